@@ -87,6 +87,28 @@ def gate_gemm_flops(B, T, K, N, layers):
     return 2.0 * layers * 2 * 2 * (4 * H) * (N + H) * (B * T * K)
 
 
+DUMP_WEIGHT_SAMPLE = 1 << 22     # f32 weights written by --dump-outputs: 16 MB, whatever the model's size (C2: 37.8 M, C4: 103 M)
+
+
+def weight_sample(flat):
+    """A fixed sample of a flat weight vector: the same DUMP_WEIGHT_SAMPLE indices (seed 0, ascending) in every run at the same size."""
+    n = flat.numel()
+    if n <= DUMP_WEIGHT_SAMPLE:
+        return flat
+    idx = torch.randint(n, (DUMP_WEIGHT_SAMPLE,), generator=torch.Generator(device="cpu").manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float32 tensors as float32 and everything else as float64, so that two builds can be
+    compared output for output on the same seeded inputs."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), (t if t.dtype == torch.float32 else t.double()).numpy())
+
+
 def _cpu_baseline_worker(seconds, fs=16000):
     """child process: one oracle (CPU torch restatement of train_se.py) optimisation step at BASELINE.json configs[0]:
     conf/models/BSRNN_baseline.yaml hyper-parameters (N = 196, 6 layers, AdamW 1e-3, clip 0.5), 8 utterances @ 16 kHz (or, fs = 48000,
@@ -189,9 +211,10 @@ def inference_forward_bench(args, dev):
     return res
 
 
-def flow_bench(dev, steps=3, single_rank_collectives=False):
+def flow_bench(dev, steps=3, single_rank_collectives=False, dump_dir=None):
     """BASELINE.json configs[3]: BSRNN-Flow (n_fft 1536 / hop 384, N = 384, 6 layers) generative train step at the
-    yaml's batch (2 x 4 s @ 48 kHz: forward_step + backward + clip + AdamW + EMA) and the Euler sampler (N = 15) on one utterance."""
+    yaml's batch (2 x 4 s @ 48 kHz: forward_step + backward + clip + AdamW + EMA) and the Euler sampler (N = 15) on one utterance.
+    dump_dir: write the last timed step's loss and weights and the sampler's waveforms there (--dump-outputs)."""
     try:
         from urgent2026_challenge_track1_amd.config import Config
         from urgent2026_challenge_track1_amd.flow_model import FlowSEModel
@@ -251,6 +274,9 @@ def flow_bench(dev, steps=3, single_rank_collectives=False):
             de16 = repr(ex16)[:120]
         finally:
             m.dnn.compute_dtype = torch.bfloat16
+        if dump_dir is not None:
+            dump_outputs(dump_dir, dict({"loss": loss, "weights": weight_sample(m.dnn.flat_params), "enhanced": out},
+                                        **({"enhanced_f16": out16} if fin16 is not None else {})))
         T, K, N = L // 384 + 1, 48, 384
         dnn_flops = 2.0 * 6 * 2 * 2 * (4 * 2 * N) * (N + 2 * N) * (T * K)          # gate GEMMs of one DNN evaluation
         res = {"workload": "BSRNN-Flow N=384 L=6 (103 M parameters), B2 x 4 s @ 48 kHz train step; Euler N=15 on 1 x 4 s",
@@ -270,6 +296,8 @@ def flow_bench(dev, steps=3, single_rank_collectives=False):
         torch.cuda.empty_cache()
         return res
     except Exception as ex:
+        if dump_dir is not None:
+            raise
         return {"error": repr(ex)}
 
 
@@ -690,7 +718,12 @@ def main():
     ap.add_argument("--dynamic-mix", action="store_true",
                     help="config C3's feed: every step draws B recipes (DynamicMixingDataset) and simulates the batch on the GPU "
                          "inside the timed region")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0): the loss, the logged SI-SNR and "
+                         "gradient norm and a fixed sample of the updated weights; --model flow: loss, weights, the sampler's waveforms")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_worker:
         _cpu_baseline_worker(args.cpu_baseline_seconds, args.cpu_baseline_fs)
         return
@@ -737,7 +770,7 @@ def main():
 
     if args.model == "flow":
         if rank == 0:
-            fb = flow_bench(dev, steps=args.steps, single_rank_collectives=use_dist and world == 1)
+            fb = flow_bench(dev, steps=args.steps, single_rank_collectives=use_dist and world == 1, dump_dir=args.dump_outputs)
             print(json.dumps({"metric": "utterances/sec (4 s @ 48 kHz) BSRNN-Flow train step", "value": fb.get("train_utt_per_s"),
                               "unit": "utt/s", "n_gpus": 1, "steps": args.steps, "warmup": 1,
                               "ms_per_step": fb.get("train_ms_per_step"), "higher_is_better": True, "scaling": "weak",
@@ -838,6 +871,9 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         sync_ok = bool(torch.equal(hi, lo))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "sisnr": model.logged["train_sisnr"], "grad_norm": model.logged["Grad_norm"],
+                                         "weights": weight_sample(core.flat_params)})
     kt = {n: (sum(a.elapsed_time(b) for a, b in v) / max(1, len(v)), len(v)) for n, v in timing.items()}
 
     T, Fb, K = L // 480 + 1, 481, 34

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from urgent2026_challenge_track1_amd import ops
 dev = "cuda"
 N, B, T, K = 196, 32, 401, 34

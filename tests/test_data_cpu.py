@@ -135,7 +135,7 @@ def _speechy(rng, n, ch, bits):
     return np.round(x).astype(np.int64)
 
 
-def test_flac_decoder_reads_every_subframe_and_stereo_mode(tmp_path):
+def test_flac_decoder_reads_every_subframe_and_stereo_mode(lib, tmp_path):
     """the library's host-side FLAC decoder (csrc/flac.hip) against streams written by tests/flac_writer.py: every subframe
     type, Rice with 4- / 5-bit parameters, partition orders, an escape partition, wasted bits, all stereo decorrelations,
     16- and 24-bit, an odd last block.  (No FLAC file or encoder exists in the image: encoder and decoder both follow the

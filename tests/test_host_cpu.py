@@ -182,7 +182,7 @@ def test_bench_gpus_n_launches_n_ranks_without_torchrun():
     assert r.returncode == 2 and json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 64
 
 
-def test_bench_weight_stream_bound_arithmetic():
+def test_bench_weight_stream_bound_arithmetic(lib):
     """the supplementary bound of the bench line (recurrent weights streamed from L2 once per step and workgroup): bytes per launch,
     workgroup counts of the two BPTT geometries, the per-CU figure against 34.5 TB/s / 256; forward kernels have none."""
     import bench
@@ -196,7 +196,25 @@ def test_bench_weight_stream_bound_arithmetic():
     assert bench.l2_port_roofline("lstm_fwd_time", 3.5, B, T, K, H) is None
 
 
-def test_flow_split_bptt_plan_does_not_depend_on_the_nsplit_shadow_size(monkeypatch):
+def test_bench_dump_outputs_files(tmp_path):
+    """--dump-outputs: one .npy per array, float32 kept and everything else widened to float64; weight vectors above the sample size are
+    written as the same seeded sample in every run (16 MB), smaller ones whole.  The step itself under -m gpu:
+    tests/test_train_gpu.py."""
+    import bench
+    flat = torch.arange(5_000_000, dtype=torch.float32)
+    s1, s2 = bench.weight_sample(flat), bench.weight_sample(flat.clone())
+    assert s1.numel() == bench.DUMP_WEIGHT_SAMPLE and s1.numel() * 4 <= 16 << 20 and torch.equal(s1, s2)
+    assert bool((s1[1:] >= s1[:-1]).all()) and s1.min() >= 0 and s1.max() < flat.numel()
+    assert torch.equal(bench.weight_sample(flat[:1000]), flat[:1000])
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": torch.tensor(1.5), "norm": torch.tensor(2.0, dtype=torch.float64),
+                                            "h": torch.ones(3, dtype=torch.bfloat16), "weights": s1})
+    got = {f: np.load(tmp_path / "d" / f) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert sorted(got) == ["h.npy", "loss.npy", "norm.npy", "weights.npy"]
+    assert got["loss.npy"].dtype == np.float32 and got["loss.npy"] == 1.5 and got["norm.npy"].dtype == np.float64
+    assert got["h.npy"].dtype == np.float64 and np.array_equal(got["weights.npy"], s1.numpy())
+
+
+def test_flow_split_bptt_plan_does_not_depend_on_the_nsplit_shadow_size(lib, monkeypatch):
     """VERDICT r4 item 5 (the 87.8 -> 104.3 ms regression of the flow train step): the second queue's sizing beside the N-split BPTT
     (TN_SHADOW_WGS_NSPLIT) must not reach the flow model, whose cooperative split BPTT is planned on the CUs the second queue leaves.  The
     plan queries need no GPU (256 CUs assumed)."""
@@ -218,7 +236,7 @@ def test_flow_split_bptt_plan_does_not_depend_on_the_nsplit_shadow_size(monkeypa
     assert len(plans) == 1 and next(iter(plans))[0] == 12, plans                             # the 12-way split of the benchmarked flow step
 
 
-def test_no_cooperative_plan_when_ranks_share_a_gpu(monkeypatch):
+def test_no_cooperative_plan_when_ranks_share_a_gpu(lib, monkeypatch):
     """two processes on one GPU (the gloo test path) must not each bring a cooperative grid - clusters that spin until every member
     has arrived cannot be co-resident with another process's.  With ops.SHARED_GPU_RANKS > 1 every cooperative plan (cluster, cluster2, split,
     N-split) is refused and the streaming kernels run; alone on the device the C2 / C4 plans exist.  The plan queries need no GPU."""

@@ -78,7 +78,7 @@ def test_fit_checkpoint_inference_roundtrip(lib, tmp_path):
     assert (tmp_path / "out" / "inf.scp").read_text().split()[0] == "utt1"
 
 
-def test_two_ranks_on_one_gpu_hold_identical_weights():
+def test_two_ranks_on_one_gpu_hold_identical_weights(lib):
     """the N > 1 path of bench.py (broadcast, bucketed all-reduce driven by the backward's ready tags, deferred wgrads on
     the second queue) with two gloo ranks sharing cuda:0 and different data per rank: after the steps both hold the same
     weights bit for bit"""
@@ -96,7 +96,7 @@ def test_two_ranks_on_one_gpu_hold_identical_weights():
     assert d["config"]["global_batch"] == 4
 
 
-def test_bench_gpus_2_starts_its_own_ranks():
+def test_bench_gpus_2_starts_its_own_ranks(lib):
     """`python bench.py --gpus 2` with NO torchrun in the command: the parent starts the two ranks itself (child process group),
     relays rank 0's line, and the line says n_gpus 2 (--gpus was parsed and never read).  gloo lets both ranks share
     the one GPU of this box; `--dynamic-mix` puts config C3's on-GPU simulator feed into the N > 1 step."""
@@ -113,24 +113,30 @@ def test_bench_gpus_2_starts_its_own_ranks():
 
 
 @pytest.mark.gpu
-def test_single_rank_rccl_carries_the_gradient_buckets():
+def test_single_rank_rccl_carries_the_gradient_buckets(lib, tmp_path):
     """The RCCL leg of the N > 1 step on a 1-GPU box: `--single-rank-collectives` creates the `nccl` (= RCCL) process group with one
     rank and sends the weight broadcast, every gradient bucket (async, on the reducer's stream, beside the backward's kernels), the
     barriers and the checksum reductions through it.  The step must issue one collective per bucket and step, end with the loss
     the plain one-GPU run ends with, and the line must say backend nccl.  (Two RCCL ranks cannot share a device; the two-rank
-    arithmetic is covered over gloo above.)"""
+    arithmetic is covered over gloo above.)  Both runs write what their last timed step computed (--dump-outputs)."""
     import json, os, subprocess, sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NCCL_MAX_NCHANNELS")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pretouch-gib", "0",
             "--batch", "2", "--seconds", "1", "--channels", "32", "--layers", "2", "--no-flow", "--no-metrics", "--no-cpu-baseline", "--no-dist-leg"]
     lines = []
-    for extra in ([], ["--single-rank-collectives", "--dist-backend", "nccl"]):
-        r = subprocess.run(base + extra, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    for i, extra in enumerate(([], ["--single-rank-collectives", "--dist-backend", "nccl"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / str(i))], cwd=root, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
         lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
     plain, rccl = lines
+    dumps = [{k: np.load(tmp_path / str(i) / (k + ".npy")) for k in ("loss", "sisnr", "grad_norm", "weights")} for i in range(2)]
+    for d, line in zip(dumps, lines):
+        assert float(d["loss"]) == line["final_loss"] and d["loss"].dtype == np.float32, (float(d["loss"]), line["final_loss"])
+        assert np.isfinite(d["sisnr"]) and d["grad_norm"] > 0 and d["weights"].dtype == np.float32 and np.isfinite(d["weights"]).all()
+    assert dumps[0]["weights"].shape == dumps[1]["weights"].shape
     assert plain["config"]["dist_backend"] is None and "gradient_buckets" not in plain
     assert rccl["config"]["dist_backend"] == "nccl" and rccl["n_gpus"] == 1 and rccl["ranks_hold_identical_weights"] is True
     gb = rccl["gradient_buckets"]
@@ -139,17 +145,19 @@ def test_single_rank_rccl_carries_the_gradient_buckets():
     assert abs(rccl["final_loss"] - plain["final_loss"]) <= 1e-3 * abs(plain["final_loss"]), (rccl["final_loss"], plain["final_loss"])
 
 
-def test_cooperative_bptt_beside_rccl_buckets_leaves_the_collective_its_cus():
+def test_cooperative_bptt_beside_rccl_buckets_leaves_the_collective_its_cus(lib, tmp_path):
     """the flow model's backward runs the COOPERATIVE split BPTT (every workgroup must be resident) while the
     reducer's all-reduce kernels occupy CUs.  From the first bucket to finish() `ops.reserved_cus()` includes RCCL's channel cap
     (NCCL_MAX_NCHANNELS is capped before the communicator exists), so the split kernel is planned on the remaining CUs or refused
-    (counted) - never launched on a grid that cannot be co-resident.  Run: BSRNN-Flow C4 train steps through a single-rank RCCL group."""
+    (counted) - never launched on a grid that cannot be co-resident.  Run: BSRNN-Flow C4 train steps through a single-rank RCCL group,
+    which also writes what its last timed step and the sampler computed (--dump-outputs)."""
     import json, os, subprocess, sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NCCL_MAX_NCHANNELS")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--model", "flow", "--gpus", "1", "--steps", "2", "--pretouch-gib", "0",
-           "--single-rank-collectives", "--dist-backend", "nccl"]
+           "--single-rank-collectives", "--dist-backend", "nccl", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -163,10 +171,13 @@ def test_cooperative_bptt_beside_rccl_buckets_leaves_the_collective_its_cus():
     lc = co["launch_counts"]
     assert lc.get("lstm_bwd_split", 0) + lc.get("lstm_bwd_stream16", 0) + lc.get("lstm_bwd_stream32", 0) > 0, co
     assert fb["final_loss"] == fb["final_loss"]
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in ("loss", "weights", "enhanced", "enhanced_f16")}
+    assert float(d["loss"]) == fb["final_loss"] and d["weights"].shape == (1 << 22,), (float(d["loss"]), d["weights"].shape)
+    assert d["enhanced"].size == d["enhanced_f16"].size == 192000 and np.isfinite(d["enhanced"]).all(), d["enhanced"].shape
 
 
 @pytest.mark.gpu
-def test_full_size_c2_step_as_one_rccl_rank_runs_the_cooperative_kernels_beside_the_buckets():
+def test_full_size_c2_step_as_one_rccl_rank_runs_the_cooperative_kernels_beside_the_buckets(lib):
     """VERDICT r5 item 1 (reference `baseline_code/train_se.py:74-83`, Lightning DDP): what ONE rank of a DDP job runs, at the size
     bench.py times (B 32 x 4 s @ 48 kHz, N 196, 6 layers) - the step as the only rank of an RCCL process group.  Every gradient bucket is
     all-reduced on the reducer's stream beside the backward; from the first bucket to finish() `ops.COMM_RESERVED_CUS` = the RCCL
@@ -257,7 +268,7 @@ def test_inference_half_default_on_a_trained_checkpoint_validated_and_with_a_way
 
 
 @pytest.mark.gpu
-def test_default_bench_line_carries_the_one_rccl_rank_leg():
+def test_default_bench_line_carries_the_one_rccl_rank_leg(lib):
     """`python bench.py` (no --no-dist-leg): after the timed steps the parent starts the SAME workload once more as the only rank of an RCCL process
     group (child process, timeout) and reports it under `config.dist`: `reserved_step_ms`, its ratio to the plain step, the buckets, the
     cooperative kernels' error flag and refusals.  Toy size here; the full-size figures are in the driver's line."""
