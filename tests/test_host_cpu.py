@@ -226,12 +226,12 @@ def test_flow_split_bptt_plan_does_not_depend_on_the_nsplit_shadow_size(lib, mon
     plans = set()
     for v in (84, 98, 112, 140):
         monkeypatch.setattr(ops, "TN_SHADOW_WGS_NSPLIT", v)
-        assert ops.use_nsplit_bwd(768, 768, torch.bfloat16, "t", sm_flow) is False         # H = 768 has no N-split kernel
+        assert ops.lstm_bwd_kernel(768, 768, 384, 384, torch.bfloat16, "t", sm_flow) != "nsplit"    # H = 768 has no N-split kernel
         target = ops.wgrad_shadow_wgs("t", False)
         assert target == ops.TN_SHADOW_WGS
         with ops.reserve_cus(co_resident=target):
             plans.add(tuple(ops.lstm_split_plan(768, sm_flow["n_seq"])))
-        assert ops.use_nsplit_bwd(392, 416, torch.bfloat16, "t", sm_c2) is True and ops.wgrad_shadow_wgs("t", True) == v
+        assert ops.lstm_bwd_kernel(392, 416, 196, 224, torch.bfloat16, "t", sm_c2) == "nsplit" and ops.wgrad_shadow_wgs("t", True) == v
         assert ops.wgrad_shadow_wgs("f", True) == ops.TN_SHADOW_WGS_BAND
     assert len(plans) == 1 and next(iter(plans))[0] == 12, plans                             # the 12-way split of the benchmarked flow step
 

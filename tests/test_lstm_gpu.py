@@ -505,12 +505,18 @@ def test_nsplit_bptt_matches_streaming_kernel(lib, B, T, K):
 
 def test_multi_pack_equals_per_lstm_pack(lib):
     """urse_lstm_pack*_multi (one launch per layout for all LSTMs of a model, what every step after the first runs) writes exactly what the
-    per-LSTM entry points write, at the C2 widths (N = 196, H = 392), for rows with different optional layouts (time / band path)."""
+    per-LSTM entry points write, at the C2 widths (N = 196, H = 392), for rows with different optional layouts (time / band path), and at the
+    C4 widths (N = 384, H = 768: whhq only) and in f32 (no optional layout)."""
     from urgent2026_challenge_track1_amd import ops
-    N, H, dt = 196, 392, torch.bfloat16
+    for N, H, dt, lays in ((196, 392, torch.bfloat16, ({"whhq", "whhb"}, {"whhq", "whhb", "wx"}, {"wx"})),
+                           (384, 768, torch.bfloat16, ({"whhq"}, {"whhq"})), (16, 32, torch.float32, (set(), set()))):
+        _check_multi_pack(ops, N, H, dt, lays)
+
+
+def _check_multi_pack(ops, N, H, dt, lays):
     g = torch.Generator(device="cuda").manual_seed(5)
     entries, want = [], []
-    for i, lay in enumerate(({"whhq", "whhb"}, {"whhq", "whhb", "wx"}, {"wx"})):
+    for i, lay in enumerate(lays):
         w = [torch.randn(8 * H, N, device="cuda", generator=g), torch.randn(8 * H, H, device="cuda", generator=g),
              torch.randn(8 * H, device="cuda", generator=g), torch.randn(8 * H, device="cuda", generator=g)]
         ref = ops.lstm_pack(*w, N, H, dt, layouts=lay)

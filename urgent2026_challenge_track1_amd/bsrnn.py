@@ -363,47 +363,25 @@ class BSRNNCore(nn.Module):
         for key, hd in h.items():
             name = key[0] if isinstance(key, tuple) else key
             pk[key] = _view(bt if name.endswith("T") else bn, hd)
-        N = self.N
+        N, d = self.N, self._dims
         if not hasattr(self, "_lstm_bufs") or self._lstm_bufs.get("key") != (dtype, self._flat.device):
             self._lstm_bufs = {"key": (dtype, self._flat.device)}
         names = ["l%d%s." % (l, path) for l in range(self.num_layer) for path in "tf"]
         srcs = {p: (self._p(p + "wih", 8 * H * N), self._p(p + "whh", 8 * H * H), self._p(p + "bih", 8 * H), self._p(p + "bhh", 8 * H))
                 for p in names}
-        multi = (ops.PACK_MULTI and self._flat.is_cuda and all(p in self._lstm_bufs for p in names) and
-                 all(set(k for k in ("whhq", "whhb", "wx", "whhb_rw", "whhTq", "wihq") if self._lstm_bufs[p].get(k) is not None) ==
-                     self._lstm_layouts(p[-2]) <= {"whhq", "whhb", "wx", "wihq"} for p in names))
+        lays = {path: ops.lstm_layouts(H, d["Hp"], N, d["Np"], dtype, path) for path in "tf"}
+        multi = ops.PACK_MULTI and self._flat.is_cuda and all(
+            p in self._lstm_bufs and lays[p[-2]] <= self._lstm_bufs[p].keys() and lays[p[-2]] <= ops.PACK_MULTI_LAYOUTS for p in names)
         if multi:
             # the buffers exist (every step after the first): one launch per layout for all 12 LSTMs instead of three to five per LSTM
             self._lstm_bufs["table"] = ops.lstm_pack_multi([srcs[p] + (self._lstm_bufs[p],) for p in names], N, H, dtype,
                                                            table=self._lstm_bufs.get("table"))
-        for l in range(self.num_layer):
-            for path in "tf":
-                p = "l%d%s." % (l, path)
-                lp = self._lstm_bufs[p] if multi else ops.lstm_pack(*srcs[p], N, H, dtype, out=self._lstm_bufs.get(p),
-                                                                    layouts=self._lstm_layouts(path))
-                self._lstm_bufs[p] = lp
-                pk[p + "wih"], pk[p + "wihT"], pk[p + "bias"] = lp["wih"], lp["wihT"], lp["bias"]
-                pk[p + "whh"], pk[p + "whhT"] = lp["whh"], lp["whhT"]
-                pk[p + "whhq"], pk[p + "whhTq"] = lp.get("whhq"), lp.get("whhTq")
-                pk[p + "wihq"] = lp.get("wihq")
-                pk[p + "whhb"] = lp.get("whhb")
-                pk[p + "whhb_rw"] = lp.get("whhb_rw")
-                pk[p + "wx"] = lp.get("wx")
+        for p in names:
+            lp = self._lstm_bufs[p] if multi else ops.lstm_pack(*srcs[p], N, H, dtype, out=self._lstm_bufs.get(p), layouts=lays[p[-2]])
+            self._lstm_bufs[p] = lp
+            pk.update((p + k, v) for k, v in lp.items() if torch.is_tensor(v))
         self._packed = pk
         self._packed_version = self.param_version
-
-    def _lstm_layouts(self, path):
-        """optional weight layouts this half layer's dispatch can reach (ops.model_lstm_layouts, narrowed by the path where the kernels are
-        path-specific at this hidden size: the fused row-wave forward and its unfused fallbacks serve many short sequences, i.e. the band path)."""
-        lay = ops.model_lstm_layouts()
-        if self.compute_dtype == torch.float16:
-            lay &= {"whhq", "wihq", "wx"}          # what ops.lstm_pack produces for f16 operands (ADVICE r5: the set never matched, 12 LSTMs were re-packed one by one)
-        if self.H == 392 and path == "t":
-            lay -= {"wx", "whhb_rw"}
-        d = self._dims
-        if (self.H == 392 and path == "f" and not ops.BAND_CLUSTERX) or not ops.lstm_clusterx_supported(self.N, d["Np"], self.H, d["Hp"]):
-            lay -= {"wihq"}          # (the fused cluster forward: the time path, and - round 6, in rounds - the band path; other shapes have no such kernel)
-        return lay
 
     def _band_tables(self, F, dtype, device):
         key = (F, dtype, device)
@@ -526,62 +504,32 @@ class BSRNNCore(nn.Module):
             two = False
         xn, stats, xn_b = ops.groupnorm_fwd(skip, self._p(p + "gamma", N), self._p(p + "beta", N), B, T, 1, K * N, N,
                                             d["Np"], 0, dt, GN_EPS, add=temb, stats=pre, bf16_copy=two or None)
-        cx_ok = (ops.USE_CLUSTERX_LSTM and ops.USE_CLUSTER_LSTM and dt in ops.HALF_TYPES and pk.get(p + "wihq") is not None and
-                 pk.get(p + "whhq") is not None and H not in ops.CLUSTER2_H and not (path == "f" and ops.BAND_PATH_NO_CLUSTER) and
-                 ops.lstm_clusterx_supported(N, d["Np"], H, d["Hp"]))
-        # the band path in ROUNDS through the fused cluster forward (round 6), where the plan's rounds x steps price below the row-wave kernel
-        band_cx = cx_ok and path == "f" and ops.BAND_CLUSTERX and ops.band_clusterx_pays(H, d["Hp"], sm["n_seq"], sm["seq_len"])
-        fused = (not band_cx and ops.USE_RWX_LSTM and ops.USE_RW_LSTM and dt in ops.HALF_TYPES and pk.get(p + "wx") is not None and
-                 sm["n_seq"] >= ops.RW_MIN_SEQ and not (ops.USE_CLUSTER_LSTM and not (path == "f" and ops.BAND_PATH_NO_CLUSTER) and
-                                                      ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is not None))
-        # (fused: the input projection runs inside the recurrence kernel - no gate GEMM, no [M, 8H] pre-activation matrix)
-        # (the time path above the clusters' capacity - more than 33 utterances per GPU at 48 kHz - in rounds too, instead of gate GEMM + streaming forward)
-        time_cx = (cx_ok and path == "t" and ops.TIME_CLUSTERX_ROUNDS and ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is None and
-                   ops.lstm_clusterx_plan(H, d["Hp"], sm["n_seq"]) is not None)
-        fused_c = not fused and cx_ok and (band_cx or time_cx or ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is not None)
-        gx = None if (fused or fused_c) else ops.gemm_nt(xn, pk[p + "wih"], pk[p + "bias"])
-        hout_b = None
-        if fused_c:
-            # the cluster forward with the projection fused (the time path at C2)
-            r = ops.lstm_fwd_clusterx(xn, pk[p + "wihq"], pk[p + "whhq"], pk[p + "bias"], N, H, d["Hp"], save=save, bf16_copy=two, **sm)
+        Hp = d["Hp"]
+        kern = ops.lstm_fwd_kernel(H, Hp, N, d["Np"], dt, path, sm, two)
+        if kern == "clusterx":          # (clusterx, rwx: the input projection runs inside the recurrence kernel - no gate GEMM, no gx matrix)
+            r = ops.lstm_fwd_clusterx(xn, pk[p + "wihq"], pk[p + "whhq"], pk[p + "bias"], N, H, Hp, save=save, bf16_copy=two, **sm)
             gx, hout, c, self._cluster_err = r[:4]
-            hout_b = r[4] if two else None
-        elif fused:
-            r = ops.lstm_fwd_rwx(xn, pk[p + "wx"], pk[p + "bias"], N, H, d["Hp"], save=save, bf16_copy=two, **sm)
+        elif kern == "rwx":
+            r = ops.lstm_fwd_rwx(xn, pk[p + "wx"], pk[p + "bias"], N, H, Hp, save=save, bf16_copy=two, **sm)
             gx, hout, c = r[:3]
-            hout_b = r[3] if two else None
-        elif dt == torch.float16:
-            # f16 operands: the cluster forward where its plan fits (the time path at C2; H = 768, the flow DNN, forward only), else the streaming kernel
-            if ops.USE_CLUSTER_LSTM and pk.get(p + "whhq") is not None and H in ops.CLUSTER2_H and not two and \
-                    ops.lstm_cluster2_chunks(H, d["Hp"], **sm) is not None:
-                r = ops.lstm_fwd_cluster2(gx, pk[p + "whhq"], H, d["Hp"], save=save, **sm)
-                hout, c, self._cluster_err = r
-            elif ops.USE_CLUSTER_LSTM and pk.get(p + "whhq") is not None and H not in ops.CLUSTER2_H and not (path == "f" and ops.BAND_PATH_NO_CLUSTER) and \
-                    ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is not None:
-                r = ops.lstm_fwd_cluster(gx, pk[p + "whhq"], H, d["Hp"], save=save, bf16_copy=two, **sm)
-                hout, c, self._cluster_err = r[:3]
-            else:
-                r = ops.lstm_fwd(gx, pk[p + "whh"], H, d["Hp"], save=save, bf16_copy=two, **sm)
-                hout, c = r[:2]
-            hout_b = r[-1] if two else None
-            gx = gx.view(torch.bfloat16)          # the kernels wrote the gate activations back in bf16 (the BPTT's operand format)
-        elif ops.USE_CLUSTER_LSTM and pk.get(p + "whhq") is not None and H in ops.CLUSTER2_H and \
-                ops.lstm_cluster2_chunks(H, d["Hp"], **sm) is not None:
-            hout, c, err = ops.lstm_fwd_cluster2(gx, pk[p + "whhq"], H, d["Hp"], save=save, **sm)
-            self._cluster_err = err
-        elif ops.USE_CLUSTER_LSTM and pk.get(p + "whhq") is not None and not (path == "f" and ops.BAND_PATH_NO_CLUSTER) and \
-                ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is not None:
-            hout, c, err = ops.lstm_fwd_cluster(gx, pk[p + "whhq"], H, d["Hp"], save=save, **sm)
-            self._cluster_err = err
-        elif ops.USE_RW_LSTM and pk.get(p + "whhb") is not None and sm["n_seq"] >= ops.RW_MIN_SEQ and ops.lstm_rw_supported(H, d["Hp"]):
-            if ops.RW_PAIRED and pk.get(p + "whhb_rw") is not None:
-                hout, c = ops.lstm_fwd_rw(gx, pk[p + "whhb_rw"], H, d["Hp"], save=save, paired=True, **sm)
-            else:
-                hout, c = ops.lstm_fwd_rw(gx, pk[p + "whhb"], H, d["Hp"], save=save, **sm)
-        elif ops.USE_WIDE_LSTM and pk.get(p + "whhb") is not None and sm["n_seq"] >= ops.WIDE_MIN_SEQ:
-            hout, c = ops.lstm_fwd_wide(gx, pk[p + "whhb"], H, d["Hp"], save=save, **sm)
         else:
-            hout, c = ops.lstm_fwd(gx, pk[p + "whh"], H, d["Hp"], save=save, **sm)
+            gx = ops.gemm_nt(xn, pk[p + "wih"], pk[p + "bias"])
+            if kern == "cluster2":
+                r = ops.lstm_fwd_cluster2(gx, pk[p + "whhq"], H, Hp, save=save, **sm)
+            elif kern == "cluster":
+                r = ops.lstm_fwd_cluster(gx, pk[p + "whhq"], H, Hp, save=save, bf16_copy=two, **sm)
+            elif kern == "rw":
+                r = ops.lstm_fwd_rw(gx, pk[p + "whhb"], H, Hp, save=save, **sm)
+            elif kern == "wide":
+                r = ops.lstm_fwd_wide(gx, pk[p + "whhb"], H, Hp, save=save, **sm)
+            else:
+                r = ops.lstm_fwd(gx, pk[p + "whh"], H, Hp, save=save, bf16_copy=two, **sm)
+            hout, c = r[:2]
+            if kern in ("cluster2", "cluster"):
+                self._cluster_err = r[2]
+            if dt == torch.float16:
+                gx = gx.view(torch.bfloat16)          # the kernels wrote the gate activations back in bf16 (the BPTT's operand format)
+        hout_b = r[-1] if two else None
         out = torch.empty_like(skip)
         if ops.FUSE_GN_STATS and dt in ops.HALF_TYPES and N % 4 == 0 and not (path == "f" and l == self.num_layer - 1):
             # the next half layer normalises `out` over each batch element (T * K rows): its sums ride on this GEMM's epilogue
@@ -607,19 +555,21 @@ class BSRNNCore(nn.Module):
         ops.gemm_nt(doT, pk[p + "wfcT"], out=dh, N=2 * H)
         sm = self._seqmap(path, B, T, K)
         overlap = ops.TN_OVERLAP and skip.is_cuda
-        use_nsplit = ops.use_nsplit_bwd(H, d["Hp"], dt, path, sm, pk.get(p + "whhTq") is not None)
-        if overlap and (path == "t" or ops.TN_OVERLAP_BAND):
-            # the time path's BPTT occupies 136 of the 256 CUs for ~7 ms (and the band path's last round of workgroups
-            # leaves most CUs idle): the weight-gradient GEMMs deferred by the previous half layers run beside it on a
-            # second stream (they only feed the optimizer / all-reduce)
-            self._run_deferred_wgrads(skip.device, ops.wgrad_shadow_wgs(path, use_nsplit), None if path == "t" else ops.TN_BAND_PARTS)
-        if ops.USE_CLUSTER_LSTM_BWD and pk.get(p + "whhTq") is not None and \
-                ops.lstm_cluster_plan(H, d["Hp"], sm["n_seq"]) is not None:
+        limit = None if path == "t" else ops.TN_BAND_PARTS
+        # the time path's BPTT occupies 136 of the 256 CUs for ~7 ms (and the band path's last round of workgroups leaves most CUs idle): the
+        # weight-gradient GEMMs deferred by the previous half layers run beside it on a second stream (they only feed the optimizer / all-reduce)
+        shadow = overlap and (path == "t" or ops.TN_OVERLAP_BAND) and bool(self._deferred) and limit != 0
+        # the cooperative BPTT kernels are planned beside the workgroups that stream will hold (those sized for the N-split, which does not
+        # reserve CUs for them, only where no cooperative kernel fits beside the smaller number)
+        with ops.reserve_cus(co_resident=ops.wgrad_shadow_wgs(path, False) if shadow else None):
+            kern = ops.lstm_bwd_kernel(H, d["Hp"], N, d["Np"], self.compute_dtype, path, sm)
+        if shadow:
+            self._run_deferred_wgrads(skip.device, ops.wgrad_shadow_wgs(path, kern == "nsplit"), limit)
+        if kern == "cluster":
             dg, self._cluster_err = ops.lstm_bwd_cluster(dh, gates, c, pk[p + "whhTq"], H, d["Hp"], **sm)
-        elif (ops.USE_SPLIT_LSTM_BWD or H >= ops.SPLIT_BWD_MIN_H) and dt == torch.bfloat16 and \
-                ops.lstm_split_chunks(H, **sm) is not None:
+        elif kern == "split":
             dg, self._cluster_err = ops.lstm_bwd_split(dh, gates, c, pk[p + "whhT"], H, **sm)
-        elif use_nsplit:
+        elif kern == "nsplit":
             dg, self._cluster_err = ops.lstm_bwd_nsplit(dh, gates, c, pk[p + "whhT"], H, **sm)
         else:
             dg = ops.lstm_bwd(dh, gates, c, pk[p + "whhT"], H, rows16=ops.BWD_ROWS16.get(path, 0), **sm)   # dgates, gate-interleaved columns

@@ -331,81 +331,62 @@ def gemm_nt_gnbwd(A, W, N, x, stats, gamma, dgamma, dbeta, rows_per_group, eps=1
     return dy, sums
 
 
-def model_lstm_layouts():
-    """the optional weight layouts the model's dispatch can reach with the current switches (the model re-packs 12 LSTMs after every
-    optimizer step: a layout nobody reads is a launch and a few MB of writes per LSTM and step)."""
-    lay = set()
-    if USE_CLUSTER_LSTM:
-        lay.add("whhq")
-        if USE_CLUSTERX_LSTM:
-            lay.add("wihq")
-    if USE_CLUSTER_LSTM_BWD:
-        lay.add("whhTq")
-    if USE_RW_LSTM and USE_RWX_LSTM:
-        lay.add("wx")
-    if USE_WIDE_LSTM or USE_RW_LSTM:
-        lay.add("whhb")          # (the unfused row-wave / wide forward; also what a shape without a fused kernel falls back to)
-    if USE_RW_LSTM and RW_PAIRED and not USE_RWX_LSTM:
-        lay.add("whhb_rw")
-    return lay
+# the optional weight layouts of an LSTM beside wih / wihT / bias / whh / whhT, and which of them one lstm_pack_multi launch re-packs
+LSTM_LAYOUTS = ("whhq", "wihq", "whhb", "wx", "whhTq")
+PACK_MULTI_LAYOUTS = {"whhq", "wihq", "whhb", "wx"}
+
+
+def lstm_layout_ok(name, N, Np, H, Hp, dtype):
+    """can lstm_pack produce this layout for the shape and operand type?  f16 (the forward-only format) gets whhq, wihq and wx, bf16 all of
+    them, f32 none."""
+    lib = _lib.load()
+    if dtype not in HALF_TYPES or Hp % 32:
+        return False
+    if name == "whhq":
+        return True
+    if name == "wihq":
+        return bool(lib.urse_lstm_clusterx_supported(N, Np, H, Hp))
+    if name == "wx":
+        return bool(lib.urse_lstm_rwx_supported(N, Np, H, Hp))
+    if dtype != torch.bfloat16:
+        return False
+    if name == "whhb":
+        return bool(lib.urse_lstm_wide_supported(H, Hp))
+    return name == "whhTq" and H % 8 == 0
 
 
 def lstm_pack(wih, whh, bih, bhh, N, H, dtype, out=None, layouts=None):
     """f32 nn.LSTM weights (fwd+reverse concatenated) -> dict of kernel-layout operands (see urse_lstm_pack).
-    layouts: which of the optional layouts to produce ({"whhq", "whhTq", "whhb", "whhb_rw", "wx", "wihq"}; None = all the shape supports)."""
-    want = lambda name: layouts is None or name in layouts
+    layouts: which of LSTM_LAYOUTS to produce (None = all the shape supports)."""
     dev = wih.device
     Np, Hp = kpad(N, dtype), kpad(pad_to(H, 16), dtype)
     nu = pad_to(H, 16)
-    bdt = bwd_dtype(dtype)        # dtype f16: the forward layouts (wih, whh, whhq, wx) are f16, the backward ones (wihT, whhT) bf16
+    bdt = bwd_dtype(dtype)        # dtype f16: the forward layouts (wih, whh, whhq, wx, wihq) are f16, the backward ones (wihT, whhT) bf16
     if out is None:
-            out = dict(wih=torch.empty(8 * H, Np, device=dev, dtype=dtype),
+        out = dict(wih=torch.empty(8 * H, Np, device=dev, dtype=dtype),
                    wihT=torch.empty(N, 8 * H, device=dev, dtype=bdt),
                    bias=torch.empty(8 * H, device=dev, dtype=torch.float32),
                    whh=torch.empty(2 * nu * 4 * Hp, device=dev, dtype=dtype),
                    whhT=torch.empty(2 * nu * 4 * H, device=dev, dtype=bdt), Np=Np, Hp=Hp)
-    call("lstm_pack", wih, whh, bih, bhh, out["wih"], out["wihT"], out["bias"], out["whh"], out["whhT"], N, Np, H, Hp,
-         _dt(out["wih"]), stream_ptr())
-    if dtype == torch.float16 and Hp % 32 == 0:
-        # the f16 forward mode has the kernels of the benchmarked dispatch: cluster forward (whhq) and fused row-wave forward (wx)
-        if want("whhq"):
-            if "whhq" not in out:
-                out["whhq"] = torch.empty(2 * ((H + 3) // 4) * (Hp // 32) * 512, device=dev, dtype=dtype)
-            call("lstm_pack_quads", whh, out["whhq"], H, Hp, F16, stream_ptr())
-        if want("wihq") and _lib.load().urse_lstm_clusterx_supported(N, Np, H, Hp):
-            if "wihq" not in out:
-                out["wihq"] = torch.empty(2 * ((H + 3) // 4) * (Np // 32) * 512, device=dev, dtype=dtype)
-            call("lstm_pack_quads_x", wih, out["wihq"], N, Np, H, F16, stream_ptr())
-        if want("wx") and _lib.load().urse_lstm_rwx_supported(N, Np, H, Hp):
-            if "wx" not in out:
-                out["wx"] = torch.empty(2 * ((H + 15) // 16) * (Hp // 32 + Np // 32) * 4 * 512, device=dev, dtype=dtype)
-            call("lstm_pack_blocks_x", wih, whh, out["wx"], N, Np, H, Hp, F16, stream_ptr())
-    if dtype == torch.bfloat16 and Hp % 32 == 0:
-        if want("whhq"):
-            if "whhq" not in out:
-                out["whhq"] = torch.empty(2 * ((H + 3) // 4) * (Hp // 32) * 512, device=dev, dtype=dtype)
-            call("lstm_pack_quads", whh, out["whhq"], H, Hp, BF16, stream_ptr())
-        if want("wihq") and _lib.load().urse_lstm_clusterx_supported(N, Np, H, Hp):
-            if "wihq" not in out:
-                out["wihq"] = torch.empty(2 * ((H + 3) // 4) * (Np // 32) * 512, device=dev, dtype=dtype)
-            call("lstm_pack_quads_x", wih, out["wihq"], N, Np, H, BF16, stream_ptr())
-        if want("whhb") and _lib.load().urse_lstm_wide_supported(H, Hp):
-            if "whhb" not in out:
-                out["whhb"] = torch.empty(2 * ((H + 15) // 16) * (Hp // 32) * 4 * 512, device=dev, dtype=dtype)
-            call("lstm_pack_blocks", whh, out["whhb"], H, Hp, stream_ptr())
-        if want("whhb_rw") and _lib.load().urse_lstm_rw_supported(H, Hp):
-            if "whhb_rw" not in out:
-                out["whhb_rw"] = torch.empty(2 * ((H + 15) // 16) * (Hp // 32) * 4 * 512, device=dev, dtype=dtype)
-            call("lstm_pack_blocks_rw", whh, out["whhb_rw"], H, Hp, stream_ptr())
-        if want("wx") and _lib.load().urse_lstm_rwx_supported(N, Np, H, Hp):
-            if "wx" not in out:
-                out["wx"] = torch.empty(2 * ((H + 15) // 16) * (Hp // 32 + Np // 32) * 4 * 512, device=dev, dtype=dtype)
-            call("lstm_pack_blocks_x", wih, whh, out["wx"], N, Np, H, Hp, BF16, stream_ptr())
-        if want("whhTq") and H % 8 == 0:
-            C = ((H + 3) // 4 + 13) // 14
-            if "whhTq" not in out:
-                out["whhTq"] = torch.empty(2 * C * 4 * (H // 8) * 512, device=dev, dtype=dtype)
-            call("lstm_pack_bwd_quads", whh, out["whhTq"], H, C, stream_ptr())
+    fdt = _dt(out["wih"])
+    call("lstm_pack", wih, whh, bih, bhh, out["wih"], out["wihT"], out["bias"], out["whh"], out["whhT"], N, Np, H, Hp, fdt, stream_ptr())
+    want = lambda name: (layouts is None or name in layouts) and lstm_layout_ok(name, N, Np, H, Hp, dtype)
+
+    def buf(name, n):
+        if name not in out:
+            out[name] = torch.empty(n, device=dev, dtype=dtype)
+        return out[name]
+    if want("whhq"):
+        call("lstm_pack_quads", whh, buf("whhq", 2 * ((H + 3) // 4) * (Hp // 32) * 512), H, Hp, fdt, stream_ptr())
+    if want("wihq"):
+        call("lstm_pack_quads_x", wih, buf("wihq", 2 * ((H + 3) // 4) * (Np // 32) * 512), N, Np, H, fdt, stream_ptr())
+    if want("whhb"):
+        call("lstm_pack_blocks", whh, buf("whhb", 2 * ((H + 15) // 16) * (Hp // 32) * 4 * 512), H, Hp, stream_ptr())
+    if want("wx"):
+        call("lstm_pack_blocks_x", wih, whh, buf("wx", 2 * ((H + 15) // 16) * (Hp // 32 + Np // 32) * 4 * 512), N, Np, H, Hp, fdt, stream_ptr())
+    if want("whhTq"):
+        C = ((H + 3) // 4 + 13) // 14
+        call("lstm_pack_bwd_quads", whh, buf("whhTq", 2 * C * 4 * (H // 8) * 512), H, C, stream_ptr())
     return out
 
 
@@ -691,6 +672,11 @@ def lstm_cluster2_plan(H, Hp, n_seq):
     return list(plan)
 
 
+def device_cus():
+    """CUs of the current device (the library's plan queries assume the MI355X's 256)."""
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
 def lstm_cluster2_chunks(H, Hp, n_seq, seq_len, inner, outer, stride):
     """[(first sequence, count)] launches of the generalised cluster kernel that cover n_seq sequences, or None.  One launch takes
     what the clusters resident on the chip hold (H = 768: 5 clusters x 64 sequences per direction); more sequences run as
@@ -703,8 +689,7 @@ def lstm_cluster2_chunks(H, Hp, n_seq, seq_len, inner, outer, stride):
     probe = lstm_cluster2_plan(H, Hp, 1)
     if probe is None:
         return None
-    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-    cap = max(1, (cus - reserved_cus() - 4) // 2 // probe[0]) * 64
+    cap = max(1, (device_cus() - reserved_cus() - 4) // 2 // probe[0]) * 64
     n = (n_seq + cap - 1) // cap
     if n > CLUSTER2_MAX_CHUNKS:
         return None
@@ -829,13 +814,10 @@ def lstm_rw_supported(H, Hp):
     return bool(_lib.load().urse_lstm_rw_supported(H, Hp))
 
 
-# the kernel form with two adjacent units per lane and block pair (wider, contiguous accesses); its weights come from lstm_pack_blocks_rw
-RW_PAIRED = os.environ.get("URSE_LSTM_RW_PAIRED", "0") == "1"      # (round 6: the paired form exists in variant builds only, -DURSE_EXPERIMENTS)
-
-
 def lstm_fwd_rw(gx, whhb, H, Hp, n_seq, seq_len, inner, outer, stride, save=True, target_wgs=0, paired=False):
     """row-wave LSTM forward (bf16, 16 sequences per wave, shared LDS weight ring): see csrc/lstm_rw.hip.
-    paired: whhb is the column-permuted packing of lstm_pack_blocks_rw."""
+    paired: whhb is the column-permuted packing of lstm_pack_blocks_rw (two adjacent units per lane and block pair; variant builds only,
+    -DURSE_EXPERIMENTS: the shipped library refuses it)."""
     M = gx.shape[0]
     ldh = kpad(2 * H, gx.dtype)
     hout = _hout_buffer(M, ldh, H, gx)
@@ -972,15 +954,6 @@ def lstm_nsplit_plan(H, n_seq):
     return list(plan)
 
 
-def use_nsplit_bwd(H, Hp, dt, path, sm, has_whhTq=False):
-    """does this half layer's BPTT run on the N-split kernel (bsrnn.dualpath_bwd's dispatch: after the opt-in cluster BPTT and the split BPTT of
-    big hidden sizes, before the streaming kernel)?  Only where the library has an N-split kernel for H (392)."""
-    return (not (USE_CLUSTER_LSTM_BWD and has_whhTq and lstm_cluster_plan(H, Hp, sm["n_seq"]) is not None) and
-            not ((USE_SPLIT_LSTM_BWD or H >= SPLIT_BWD_MIN_H) and dt == torch.bfloat16 and lstm_split_chunks(H, **sm) is not None) and
-            USE_NSPLIT_LSTM_BWD and dt == torch.bfloat16 and path not in BWD_ROWS16 and sm["n_seq"] <= NSPLIT_MAX_SEQ and
-            sm["n_seq"] * sm["seq_len"] >= 4096 and lstm_nsplit_plan(H, sm["n_seq"]) is not None)
-
-
 def wgrad_shadow_wgs(path, nsplit):
     """workgroups the second queue's weight-gradient launches are sized to beside this half layer's BPTT.  TN_SHADOW_WGS_NSPLIT applies ONLY
     beside the N-split kernel: every other time-path BPTT - the flow model's cooperative split BPTT among them, whose plan is made on the CUs
@@ -1051,6 +1024,77 @@ def lstm_bwd(dh, gates, c, whhT, H, n_seq, seq_len, inner, outer, stride, rows16
     timed_call(tname, "lstm_bidir_bwd", dh, dh.stride(0), gates,
                gates.stride(0), c, whhT, H, n_seq, seq_len, inner, outer, stride, _dt(gates), rows16, stream_ptr())
     return gates
+
+
+# ---------------------------------------------------------------------------------------------
+# kernel choice of a BLSTM half layer: one list of candidates per direction, in priority order, each
+# (kernel, optional layouts it reads, static condition, run-time condition).  The static part (switches, dtype, H, path, the library's
+# *_supported queries, lstm_pack's own conditions through the layouts) also decides which layouts the model packs; the run-time part
+# (plans, sequence counts) is evaluated at most once per plan and decision, so a refused cooperative plan counts once in COOP_REFUSALS.
+# ---------------------------------------------------------------------------------------------
+def _once(fn):
+    """fn() on the first call, its result after"""
+    memo = []
+
+    def get():
+        if not memo:
+            memo.append(fn())
+        return memo[0]
+    return get
+
+
+def _fwd_candidates(H, Hp, path, sm, bf16_copy, dtype):
+    band = path == "f"
+    cluster_ok = USE_CLUSTER_LSTM and not (band and BAND_PATH_NO_CLUSTER)
+    cluster = _once(lambda: lstm_cluster_plan(H, Hp, sm["n_seq"]) is not None)
+    # (H = 392: the band path reads wihq only in rounds, the time path has no wx)
+    cx = USE_CLUSTERX_LSTM and cluster_ok and H not in CLUSTER2_H and not (H == 392 and band and not BAND_CLUSTERX)
+    return [
+        # the input projection inside the recurrence (no gate GEMM, no [M, 8H] pre-activation matrix): the cluster form where one round of
+        # clusters holds the sequences, or (band path) where its rounds price below the row-wave kernel ...
+        ("clusterx", ("wihq", "whhq"), cx,
+         lambda: (band and BAND_CLUSTERX and band_clusterx_pays(H, Hp, sm["n_seq"], sm["seq_len"])) or cluster()),
+        ("rwx", ("wx",), USE_RWX_LSTM and USE_RW_LSTM and not (H == 392 and not band),
+         lambda: sm["n_seq"] >= RW_MIN_SEQ and not (cluster_ok and cluster())),
+        # ... and the time path above one round's capacity (more than 33 utterances per GPU at 48 kHz) in rounds
+        ("clusterx", ("wihq", "whhq"), cx and not band and TIME_CLUSTERX_ROUNDS, lambda: lstm_clusterx_plan(H, Hp, sm["n_seq"]) is not None),
+        ("cluster2", ("whhq",), USE_CLUSTER_LSTM and H in CLUSTER2_H,
+         lambda: not bf16_copy and lstm_cluster2_chunks(H, Hp, **sm) is not None),
+        ("cluster", ("whhq",), cluster_ok and not (dtype == torch.float16 and H in CLUSTER2_H), cluster),
+        ("rw", ("whhb",), USE_RW_LSTM and lstm_rw_supported(H, Hp), lambda: sm["n_seq"] >= RW_MIN_SEQ),
+        ("wide", ("whhb",), USE_WIDE_LSTM, lambda: sm["n_seq"] >= WIDE_MIN_SEQ),
+        ("stream", (), True, lambda: True)]
+
+
+def _bwd_candidates(H, Hp, path, sm, dtype):
+    bf16 = bwd_dtype(dtype) == torch.bfloat16
+    return [
+        ("cluster", ("whhTq",), USE_CLUSTER_LSTM_BWD, lambda: lstm_cluster_plan(H, Hp, sm["n_seq"]) is not None),
+        ("split", (), (USE_SPLIT_LSTM_BWD or H >= SPLIT_BWD_MIN_H) and bf16, lambda: lstm_split_chunks(H, **sm) is not None),
+        ("nsplit", (), USE_NSPLIT_LSTM_BWD and bf16 and path not in BWD_ROWS16,
+         lambda: sm["n_seq"] <= NSPLIT_MAX_SEQ and sm["n_seq"] * sm["seq_len"] >= 4096 and lstm_nsplit_plan(H, sm["n_seq"]) is not None),
+        ("stream", (), True, lambda: True)]
+
+
+def _static(cands, N, Np, H, Hp, dtype):
+    return [(name, lay, runs) for name, lay, ok, runs in cands if ok and all(lstm_layout_ok(x, N, Np, H, Hp, dtype) for x in lay)]
+
+
+def lstm_fwd_kernel(H, Hp, N, Np, dtype, path, sm, bf16_copy=False):
+    """forward kernel of a half layer: "clusterx", "rwx", "cluster2", "cluster", "rw", "wide" or "stream".  dtype: the compute dtype; sm: the
+    sequence map; bf16_copy: the f16 forward writes its hidden states once more in bf16 (cluster2 cannot)."""
+    return next(name for name, _, runs in _static(_fwd_candidates(H, Hp, path, sm, bf16_copy, dtype), N, Np, H, Hp, dtype) if runs())
+
+
+def lstm_bwd_kernel(H, Hp, N, Np, dtype, path, sm):
+    """BPTT kernel of a half layer whose forward ran in `dtype`: "cluster", "split", "nsplit" or "stream"."""
+    return next(name for name, _, runs in _static(_bwd_candidates(H, Hp, path, sm, dtype), N, Np, H, Hp, dtype) if runs())
+
+
+def lstm_layouts(H, Hp, N, Np, dtype, path):
+    """the optional layouts a half layer's kernels can read: the model packs these after every optimizer step, and no others."""
+    cands = _fwd_candidates(H, Hp, path, None, False, dtype) + _bwd_candidates(H, Hp, path, None, dtype)
+    return {x for _, lay, _ in _static(cands, N, Np, H, Hp, dtype) for x in lay}
 
 
 # ---------------------------------------------------------------------------------------------
