@@ -493,6 +493,28 @@ int urse_estoi_batch(const float* ref10k, const float* inf10k, float* out, float
 int urse_sdr_batch(const float* ref, const float* est, float* out, double* acf, double* xcorr, double* norms, int P,
                    int L, float clamp_db, void* stream);
 
+/* ---- audio bandwidth estimation (corpus preparation) -----------------------------------------------------------
+ * utils/estimate_audio_bandwidth.py:11-49, called by every corpus recipe (utils/prepare_ESD.sh:76-94 ...) in front of
+ * utils/resample_to_estimated_bandwidth.py, whose soxr.resample is urse_resample_poly with the soxr-HQ design. */
+/* Mean power spectrum of torch.stft (:32-44: centred, reflect padding of n_fft / 2, periodic Hann, one-sided, not normalised):
+ * wav f32 [rows, ld], lens int32 [rows] (each <= max_len <= ld; every channel of every file is a row), mean_power f32 [rows, F],
+ * F = n_fft / 2 + 1: the mean over the row's T = 1 + (len + 2 (n_fft / 2) - n_fft) / hop frames (torch.stft's count: 1 + len / hop for an
+ * even n_fft, 1 + (len - 1) / hop for an odd one) of re^2 + im^2, frames reflected at the row's OWN length.
+ * The [rows, T, F] spectrogram is never written; partial sums per frame chunk go to the workspace and are added in chunk order
+ * (no atomics: the same input gives the same bits on every run).  A row with len <= n_fft / 2 (torch.stft refuses it) gets
+ * zeros.  The reference's n_fft = int(0.032 fs) is 256 / 512 / 705 / 768 / 1024 / 1411 / 1536 at the seven challenge rates.  Runs: every
+ * n_fft <= 2048 (sizes with a prime factor >= 19, such as 705 = 3 * 5 * 47 and 1411 = 17 * 83, as Bluestein transforms in LDS) and every
+ * n_fft <= 4096 whose prime factors are <= 127; anything else: URSE_ERR_UNSUPPORTED, there is no host path.
+ * workspace: urse_power_spectrum_workspace_bytes(rows, max_len, n_fft, hop) bytes of device memory. */
+int urse_power_spectrum_workspace_bytes(int64_t rows, int max_len, int n_fft, int hop, int64_t* bytes);
+int urse_power_spectrum_mean(const float* wav, int64_t ld, const int32_t* lens, float* mean_power, int64_t rows,
+                             int max_len, int n_fft, int hop, void* workspace, int64_t workspace_bytes, void* stream);
+/* The decision of :45-49 for P files; file p owns rows [row_start[p], row_start[p + 1]) of mean_power f32 [rows, F] (row_start int32
+ * [P + 1]): peak[c] = max_f mean_power[c, f], min_energy = min_c peak[c] * 10 ** (threshold_db / 10), bin[p] (int32 [P]) = the
+ * largest i with min_c mean_power[c, i] > min_energy (strict, compared in double), -1 where no bin qualifies (an all-zero file). */
+int urse_bandwidth_pick(const float* mean_power, const int32_t* row_start, int32_t* bin, int P, int F,
+                        double threshold_db, void* stream);
+
 /* ---- BSRNN-Flow (flow-matching generative model) ---------------------------------------------------------
  * baseline_code/flow_model.py + models/bsrnn_flowse.py + models/odes.py + sampling/ (SURVEY rows a11-a14).
  * Complex tensors are interleaved f32; feature maps are channel-last [B, T, F, C]. */

@@ -59,6 +59,19 @@ def read_audio(path):
     return np.ascontiguousarray(x[:, :1].T), fs
 
 
+def read_audio_all(path):
+    """-> (float32 [C, T], fs): every channel of a WAV or FLAC file (``soundfile.read`` followed by ``.T``, as
+    utils/estimate_audio_bandwidth.py:22-31 takes it)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:4] == b"fLaC":
+        from .flac import decode_flac
+        x, fs = decode_flac(data, path)
+    else:
+        x, fs = _read_wav(data, path)
+    return np.ascontiguousarray(x.T), fs
+
+
 def audio_frames(path):
     """number of sample frames without decoding the payload where the container says so (``SoundFile.frames``)."""
     with open(path, "rb") as f:
@@ -92,5 +105,18 @@ def write_audio(path, x, fs, subtype="PCM_16"):
         pcm, tag, bits = np.clip(np.round(x * 32768.0), -32768, 32767).astype("<i2").tobytes(), 1, 16
     hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, tag, 1, fs, fs * bits // 8,
                       bits // 8, bits, b"data", len(pcm))
+    with open(path, "wb") as f:
+        f.write(hdr + pcm)
+
+
+def write_audio_channels(path, x, fs):
+    """16-bit PCM WAV of float samples [C, T] (or [T]), channels interleaved: ``soundfile.write(path, x.T, fs)`` with its default
+    subtype for .wav (utils/resample_to_estimated_bandwidth.py:75)."""
+    x = np.asarray(x, dtype=np.float32)
+    x = x[None] if x.ndim == 1 else x
+    ch = x.shape[0]
+    pcm = np.clip(np.round(x.T * 32768.0), -32768, 32767).astype("<i2").tobytes()
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, ch, fs, fs * ch * 2, ch * 2, 16,
+                      b"data", len(pcm))
     with open(path, "wb") as f:
         f.write(hdr + pcm)
