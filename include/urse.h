@@ -570,6 +570,29 @@ int urse_pesq_batch(const float* ref, const float* deg, int64_t ld, const int32_
 int urse_flac_info(const void* data, int64_t nbytes, int64_t* info);
 int urse_flac_decode(const void* data, int64_t nbytes, int32_t* out, int64_t capacity_frames, int64_t* decoded);
 
+/* ---- FLAC encoding (DEVICE kernels; mono, 16 bit) ---------------------------------------------------------------------
+ * The writer of simulation/simulate_data_from_param.py:572-586 (soundfile.write, '--out_format flac').  One workgroup per
+ * frame: CONSTANT / VERBATIM / FIXED order 0-4 by exact bit count, partitioned Rice residuals (4-bit parameter, k <= 14,
+ * partitions of whole 64-sample chunks; a short last block has one partition), fixed-blocksize frame headers with the
+ * block-size and sample-rate codes, UTF-8 frame number, CRC-8, CRC-16.  The bytes of a frame depend on its samples, length,
+ * rate and number only: the same on every run and in every batch.  'fLaC' + STREAMINFO are the caller's (flac.py). */
+/* pcm int16 [rows, ldp] = clip(rint(x * scale), -32768, 32767) of x f32 [rows, ldx] for i < lens[row] (device int32, NULL =
+ * max_len), 0 for lens[row] <= i < max_len; NaN -> 0.  scale = 32768 is the rule of the 16-bit WAV writer. */
+int urse_pcm16_from_f32(const float* x, int64_t ldx, const int32_t* lens, int16_t* pcm, int64_t ldp, int64_t rows,
+                        int max_len, float scale, void* stream);
+/* lens: HOST int32 [P].  info (host int64 [3]) = {workspace bytes, frames of the batch, upper bound of the stream bytes}. */
+int urse_flac_encode_workspace_bytes(const int32_t* lens, int P, int blocksize, int64_t* info);
+/* pcm: DEVICE int16 [total_samples]; file p is pcm[starts[p] .. starts[p] + lens[p]) at rates[p] Hz (starts int64, lens, rates
+ * int32: HOST arrays [P]).  blocksize 256 | 512 | 1024 | 2048 | 4096; channels = 1, bits = 16 and a rate of 8000, 16000, 22050,
+ * 24000, 32000, 44100 or 48000 Hz, anything else: URSE_ERR_UNSUPPORTED, nothing launched.  out (HOST, out_capacity bytes)
+ * receives the frames of file 0, file 1, ... back to back; file_bytes (host int64 [P]) and frame_bytes (host int32 [frames],
+ * file after file) their sizes.  The sizes come back first; when their sum exceeds out_capacity the call fails with
+ * URSE_ERR_INVALID_ARG, out is not touched and file_bytes is zero.  Returns after the stream has finished. */
+int urse_flac_encode(const int16_t* pcm, int64_t total_samples, const int64_t* starts, const int32_t* lens,
+                     const int32_t* rates, int P, int channels, int bits, int blocksize, void* workspace,
+                     int64_t workspace_bytes, void* out, int64_t out_capacity, int64_t* file_bytes, int32_t* frame_bytes,
+                     void* stream);
+
 /* ---- diagnostics (not on the product path) ----------------------------------------------------------------------
  * streams `bytes` of `buf` with `width`-byte (4 | 8 | 16) per-lane reads (write = 0) or writes (write = 1): a known byte
  * count to calibrate the rocprofv3 FETCH_SIZE / WRITE_SIZE counters per access width (scripts/pmc_calibrate.py). */

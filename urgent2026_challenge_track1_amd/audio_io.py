@@ -1,5 +1,5 @@
 """Audio file I/O without ``soundfile`` (absent from the image): RIFF/WAVE (PCM 16/24/32, IEEE float32) read / write and
-FLAC read (``flac.py``).  ``read_audio`` mirrors what the reference gets from ``soundfile.read(..., always_2d=True)``
+FLAC read, and mono 16-bit FLAC write through the device encoder (``flac.py``).  ``read_audio`` mirrors what the reference gets from ``soundfile.read(..., always_2d=True)``
 followed by ``audio[:, :1].T`` (simulate_data_from_param.py:347-349): float samples in [-1, 1), first channel, shape [1, T].
 """
 import struct
@@ -120,3 +120,16 @@ def write_audio_channels(path, x, fs):
                       b"data", len(pcm))
     with open(path, "wb") as f:
         f.write(hdr + pcm)
+
+
+def write_flac(path, x, fs, blocksize=4096):
+    """Mono 16-bit FLAC of float samples [T] (host array or device tensor), quantised by ``write_audio``'s rule and encoded on the device
+    (flac.py, csrc/flac_enc.hip): the file decodes to the samples ``write_audio`` would have put into a .wav."""
+    import torch
+    from .flac import encode_flac, quantise_pcm16
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
+    x = x.reshape(1, -1).to(torch.float32).cuda()
+    data = encode_flac(quantise_pcm16(x), [x.shape[1]], fs, blocksize)[0]
+    with open(path, "wb") as f:
+        f.write(data)

@@ -206,10 +206,15 @@ def _lost_packets(n_samples, fs, cfg, rs):
     return list(set(lost))       # (built exactly like this in the reference: the order of the list is the set's)
 
 
-def draw_recipe(speech_length, fs, noise_table, rir_table, wind_table, cfg=SimulationConfigs, rs=np.random):
+def draw_recipe(speech_length, fs, noise_table, rir_table, wind_table, cfg=SimulationConfigs, rs=np.random, pick=None):
     """One mixing recipe, drawn with the reference's sequence of ``np.random`` calls: wind-noise coin, number and choice
     of augmentations (re-drawn while wind noise meets clipping), noise sample, [wind-noise parameters,] SNR, RIR coin and
-    sample, per-augmentation parameters.  Returns the reference's ``info`` fields plus the parsed parameters."""
+    sample, per-augmentation parameters.  Returns the reference's ``info`` fields plus the parsed parameters.
+    ``pick(fs, table)`` replaces the nothing-is-used source choice (the offline generator passes ``select_sample`` with its used
+    pools, generate_data_param.py)."""
+    if pick is None:
+        def pick(fs, table):
+            return _pick_source(fs, table, rs)
     names = list(cfg.augmentations)
     w = np.array([cfg.augmentations[a]["weight"] for a in names], dtype=float)
     w = w / w.sum()
@@ -222,7 +227,7 @@ def draw_recipe(speech_length, fs, noise_table, rir_table, wind_table, cfg=Simul
             chosen = rs.choice(names, p=w, size=n_aug, replace=False)
     text, params = "", {}
     if wind:
-        noise_uid = _pick_source(fs, wind_table, rs)
+        noise_uid = pick(fs, wind_table)
         wc = cfg.wind_noise_config
         vals = [rs.uniform(*wc[k]) for k in ("threshold", "ratio", "attack", "release", "sc_gain", "clipping_threshold")]
         clip = rs.random() < wc["clipping_chance"]
@@ -232,7 +237,7 @@ def draw_recipe(speech_length, fs, noise_table, rir_table, wind_table, cfg=Simul
                                     clipping=clip)
         snr = rs.uniform(wc["wind_noise_snr_low_bound"], wc["wind_noise_snr_high_bound"])
     else:
-        noise_uid = _pick_source(fs, noise_table, rs)
+        noise_uid = pick(fs, noise_table)
         snr = rs.uniform(cfg.snr_low_bound, cfg.snr_high_bound)
     if noise_uid is None:
         raise ValueError("Noise sample not found for fs=%d+ Hz" % fs)
@@ -240,7 +245,7 @@ def draw_recipe(speech_length, fs, noise_table, rir_table, wind_table, cfg=Simul
     if rir_table is None or cfg.prob_reverberation <= 0.0 or rs.rand() <= cfg.prob_reverberation:
         rir_uid = None
     else:
-        rir_uid = _pick_source(fs, rir_table, rs)
+        rir_uid = pick(fs, rir_table)
     if len(chosen) == 0:
         if not wind:
             text = "none"
@@ -438,6 +443,13 @@ class RawMixBatch:
         return out, new_lens
 
     def materialise(self, device, skipped=None):
+        clean, noisy = self.simulate(device, skipped)
+        B, T = clean.shape
+        return (clean.view(B, 1, T), noisy.view(B, 1, T), torch.tensor(self.fs, dtype=torch.int32),
+                torch.tensor(self.lengths, dtype=torch.int32))
+
+    def simulate(self, device, skipped=None, return_noise=False):
+        """-> (clean, noisy[, noise]) f32 [B, T] on the device (the offline simulator stores the noise too)."""
         from . import mixing
         noise, noise_lens = self._to_batch_rate(self.noise.to(device, non_blocking=True), self.noise_lens, self.noise_fs)
         rir = None if self.rir is None else self.rir.to(device, non_blocking=True)
@@ -446,12 +458,8 @@ class RawMixBatch:
         for b, f in enumerate(self.rir_fs):
             if rir is not None and f != self.fs and rir_lens[b] > 0:
                 rir_early[b] = mixing.early_rir_stop(rir[b:b + 1, :rir_lens[b]].cpu().numpy(), self.fs)
-        out = mixing.simulate_recipes(self.speech.to(device, non_blocking=True), self.lengths, noise, noise_lens,
-                                      rir, rir_lens, rir_early, self.fs, self.recipes, skipped)
-        clean, noisy = out
-        B, T = clean.shape
-        return (clean.view(B, 1, T), noisy.view(B, 1, T), torch.tensor(self.fs, dtype=torch.int32),
-                torch.tensor(self.lengths, dtype=torch.int32))
+        return mixing.simulate_recipes(self.speech.to(device, non_blocking=True), self.lengths, noise, noise_lens,
+                                       rir, rir_lens, rir_early, self.fs, self.recipes, skipped, return_noise=return_noise)
 
 
 def collate_dynamic(items, pinned=False):

@@ -350,7 +350,7 @@ def bandwidth_limitation_resampy(speech, fs, fs_new, res_type):
     return fix(up, L)
 
 
-def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_early_stops, fs, recipes, skipped=None):
+def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_early_stops, fs, recipes, skipped=None, return_noise=False):
     """``process_one_sample(on_the_fly=True)`` (simulate_data_from_param.py:440-590) for a batch of raw sources and the
     recipes ``dataset.draw_recipe`` drew for them (one fs per batch) -> (speech, noisy) f32 [B, L].
 
@@ -360,7 +360,8 @@ def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_ear
     (polyphase, scipy / FFT, and - round 3 - resampy's kaiser_best / kaiser_fast, restated without the package); ``codec``
     (ffmpeg) and the wind-noise side-chain compressor (ffmpeg) have no device implementation: the recipe still DRAWS them (so the
     random stream matches the reference) but they are not applied - wind noise is mixed additively at its drawn SNR - and each
-    omission is counted in ``skipped``."""
+    omission is counted in ``skipped``.  ``return_noise``: -> (speech, noisy, scaled noise), what the offline simulator stores under
+    ``--store_noise``."""
     ops.require_cuda(speech, noise_raw)
     B, L = speech.shape
     dev = speech.device
@@ -421,4 +422,4 @@ def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_ear
     if speech.data_ptr() == noisy.data_ptr():
         speech = speech.clone()
     joint_peak_normalise(speech, noisy, noise)
-    return speech, noisy
+    return (speech, noisy, noise) if return_noise else (speech, noisy)
