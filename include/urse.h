@@ -415,6 +415,18 @@ int urse_resample_table(const float* x, int64_t ldx, float* y, int64_t ldy, cons
                         int n_orig, int n_out, double time_increment, double scale, int num_table, int index_step, void* stream);
 int urse_joint_peak_scale(float* speech, float* noisy, float* noise, int B, int64_t ld, float target, void* peak_scratch,
                           void* stream);
+/* urse_wind_mix (wind_noise :129-217, the filter graph of buildFFmpegCommand :60-89; csrc/wind.hip): the wind rows of a batch that has been
+ *   through urse_mix_noise.  speech = the clean target, x = the speech after high-pass / RIR (what urse_mix_noise took as `speech`), noise =
+ *   urse_mix_noise's noise_out, noisy = its noisy_out, all [B, ld] f32; rows = device int32 [nrows], the batch indices of the wind rows, each
+ *   at most once; params = device f64 [nrows, 8] = {threshold, ratio, attack ms, release ms, sc_gain, clipping_threshold, fs, has_rir}
+ *   per listed row.  For those rows, samples [0, len): noisy <- the side-chain-compressed, amix-ed, 16-bit-rounded and clipped mixture,
+ *   noise <- the 16-bit-rounded noise, speech <- c * speech when has_rir == 0 (c = 0.9 / max(max|x|, max|noise|), 1 when both are silent;
+ *   c_out = device f64 [nrows] or null receives it).  Nothing else is written.  noisy and noise must be buffers of their own; speech may
+ *   be x.  ffmpeg's sidechaincompress / amix restated from their published definition, unpinned.
+ * urse_wind_chunk: samples per LDS stage of that kernel (a row crosses a stage boundary every so many samples). */
+int urse_wind_mix(float* speech, const float* x, float* noise, float* noisy, const int32_t* lens, int B, int64_t ld, const int32_t* rows,
+                  int nrows, const double* params, double* c_out, void* stream);
+int urse_wind_chunk(void);
 /* y = a*x + b*y (f32). */
 int urse_axpby(const float* x, float* y, float a, float b, int64_t n, void* stream);
 /* y = torch.nan_to_num(x, nan=0) (baseline_code/flow_model.py:156-157): NaN -> 0, +-inf -> +-FLT_MAX; y may alias x. */

@@ -4,7 +4,7 @@ Mirrors ``baseline_code/config.py:6-72``: defaults (``:8-38``), yaml values over
 new keys, ``train_tag`` := basename of the yaml (``:41-52``), one ``--flag`` per attribute with bools parsed
 by ``str2bool`` (``:54-72``).  Extra keys: ``compute_dtype`` ("bf16" | "f16" | "f32") selects the MFMA operand type ("f16": IEEE-half operands in the forward contractions,
 bf16 in the backward - the enhanced waveform then meets 1e-3 against the f32 reference arithmetic, bsrnn.BSRNNCore);
-``unsupported_augmentation`` ("warn" | "raise" | "count") - see below.
+``unsupported_augmentation`` ("warn" | "raise" | "count") and ``wind_noise_compressor`` ("skip" | "device") - see below.
 """
 import argparse
 import os
@@ -46,6 +46,10 @@ class Config:
         # wind-noise side-chain compressor need ffmpeg): "warn" = apply the rest, warn at the first one, report counters
         # with every log line; "raise" = stop at the first one; "count" = counters only
         self.unsupported_augmentation = "warn"
+        # wind-noise rows of dynamic mixing: "skip" = mixed additively at the drawn SNR and counted as not applied (above); "device" = the
+        # reference's side-chain compressor recipe on the device (csrc/wind.hip: ffmpeg's filter restated, not pinned against the binary) -
+        # a wind draw is then no unsupported augmentation
+        self.wind_noise_compressor = "skip"
         for k, v in kwargs.items():
             setattr(self, k, v)
 

@@ -442,14 +442,15 @@ class RawMixBatch:
                 out[b, :new_lens[b]] = y[i, :new_lens[b]]
         return out, new_lens
 
-    def materialise(self, device, skipped=None):
-        clean, noisy = self.simulate(device, skipped)
+    def materialise(self, device, skipped=None, wind_compressor=False):
+        clean, noisy = self.simulate(device, skipped, wind_compressor=wind_compressor)
         B, T = clean.shape
         return (clean.view(B, 1, T), noisy.view(B, 1, T), torch.tensor(self.fs, dtype=torch.int32),
                 torch.tensor(self.lengths, dtype=torch.int32))
 
-    def simulate(self, device, skipped=None, return_noise=False):
-        """-> (clean, noisy[, noise]) f32 [B, T] on the device (the offline simulator stores the noise too)."""
+    def simulate(self, device, skipped=None, return_noise=False, wind_compressor=False):
+        """-> (clean, noisy[, noise]) f32 [B, T] on the device (the offline simulator stores the noise too).  ``wind_compressor``: wind rows
+        are mixed by the reference's side-chain compressor recipe on the device instead of additively (mixing.simulate_recipes)."""
         from . import mixing
         noise, noise_lens = self._to_batch_rate(self.noise.to(device, non_blocking=True), self.noise_lens, self.noise_fs)
         rir = None if self.rir is None else self.rir.to(device, non_blocking=True)
@@ -459,7 +460,8 @@ class RawMixBatch:
             if rir is not None and f != self.fs and rir_lens[b] > 0:
                 rir_early[b] = mixing.early_rir_stop(rir[b:b + 1, :rir_lens[b]].cpu().numpy(), self.fs)
         return mixing.simulate_recipes(self.speech.to(device, non_blocking=True), self.lengths, noise, noise_lens,
-                                       rir, rir_lens, rir_early, self.fs, self.recipes, skipped, return_noise=return_noise)
+                                       rir, rir_lens, rir_early, self.fs, self.recipes, skipped, return_noise=return_noise,
+                                       wind_compressor=wind_compressor)
 
 
 def collate_dynamic(items, pinned=False):

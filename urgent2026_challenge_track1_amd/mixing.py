@@ -1,6 +1,7 @@
 """On-device dynamic mixing: the batched counterpart of the reference's per-utterance simulator functions
 (``simulation/simulate_data_from_param.py``: ``mix_noise`` :95-126, ``add_reverberation`` :220-230, high-pass :29-56,461,
-``clipping`` :255-276, ``packet_loss`` :333-341, final peak normalisation :576-584) on the HIP kernels of csrc/mix.hip.
+``clipping`` :255-276, ``packet_loss`` :333-341, final peak normalisation :576-584) on the HIP kernels of csrc/mix.hip, and
+``wind_noise`` :129-217 (opt-in) on csrc/wind.hip.
 
 Signals are f32 ``[B, L]`` CUDA tensors with per-utterance ``lens`` (int32 CUDA); the random draws of the recipe (SNR,
 noise offset, packet indices, quantiles: ``dataset.py:232-278``) stay on the host and come in as small tensors.  The
@@ -154,6 +155,39 @@ def joint_peak_normalise(speech, noisy, noise, target=0.9):
     scratch = torch.empty(B, dtype=torch.int32, device=speech.device)
     call("joint_peak_scale", speech, noisy, noise, B, speech.stride(0), float(target), scratch, stream_ptr())
     return speech, noisy, noise
+
+
+WIND_PARAMS = ("threshold", "ratio", "attack", "release", "sc_gain", "clipping_threshold")
+
+
+def wind_chunk():
+    """samples per LDS stage of the wind-noise kernel (``urse_wind_chunk``): the lengths at which a row crosses a stage boundary"""
+    return int(_lib.load().urse_wind_chunk())
+
+
+def wind_noise(speech, x, noise, noisy, lens, rows, params, has_rir, fs):
+    """``wind_noise`` (:129-217) for the rows ``rows`` of a batch that has been through ``mix_noise``, in place (``urse_wind_mix``,
+    csrc/wind.hip): ``x`` = the speech ``mix_noise`` was given (after high-pass / RIR), ``noise`` / ``noisy`` = its two results, ``speech`` =
+    the clean target.  ``params`` = one dict per listed row with the recipe's ``threshold, ratio, attack, release, sc_gain,
+    clipping_threshold``; ``has_rir`` = one flag per listed row (without an RIR the reference rescales the clean target too, :179 with
+    :478).  The listed rows' noisy / noise (and clean) samples are rewritten, nothing else.  ffmpeg's ``sidechaincompress`` + ``amix``
+    restated from their published definition, not pinned against the binary.  -> c = 0.9 / max(max|x|, max|noise|) per listed row (f64)."""
+    ops.require_cuda(speech, x, noise, noisy)
+    rows = [int(b) for b in rows]
+    dev = speech.device
+    B = speech.shape[0]
+    if not (speech.stride(0) == x.stride(0) == noise.stride(0) == noisy.stride(0)) or any(t.stride(1) != 1 or t.dtype != torch.float32
+                                                                                       for t in (speech, x, noise, noisy)):
+        raise ValueError("wind_noise: speech, x, noise and noisy must be f32 [B, L] with one row pitch")
+    if len(set(rows)) != len(rows) or any(b < 0 or b >= B for b in rows) or not (len(rows) == len(params) == len(has_rir)):
+        raise ValueError("wind_noise: rows %s of a batch of %d with %d parameter sets, %d RIR flags" % (rows, B, len(params), len(has_rir)))
+    c = torch.empty(len(rows), dtype=torch.float64, device=dev)
+    if not rows:
+        return c
+    table = [[float(p[k]) for k in WIND_PARAMS] + [float(fs), 1.0 if h else 0.0] for p, h in zip(params, has_rir)]
+    call("wind_mix", speech, x, noise, noisy, _i32(lens, dev), B, speech.stride(0), _i32(rows, dev), len(rows),
+         _upload(table, torch.float64, dev), c, stream_ptr())
+    return c
 
 
 def early_rir_stop(rir, fs, early_rir_sec=0.05, level_ratio=1e-1):
@@ -350,7 +384,8 @@ def bandwidth_limitation_resampy(speech, fs, fs_new, res_type):
     return fix(up, L)
 
 
-def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_early_stops, fs, recipes, skipped=None, return_noise=False):
+def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_early_stops, fs, recipes, skipped=None, return_noise=False,
+                     wind_compressor=False):
     """``process_one_sample(on_the_fly=True)`` (simulate_data_from_param.py:440-590) for a batch of raw sources and the
     recipes ``dataset.draw_recipe`` drew for them (one fs per batch) -> (speech, noisy) f32 [B, L].
 
@@ -358,10 +393,15 @@ def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_ear
     each recipe's own order: pass p handles every utterance's p-th augmentation, the others ride along with identity
     parameters (quantiles 0 / 1, no packets).  ``bandwidth_limitation`` is applied with all four resamplers the reference draws
     (polyphase, scipy / FFT, and - round 3 - resampy's kaiser_best / kaiser_fast, restated without the package); ``codec``
-    (ffmpeg) and the wind-noise side-chain compressor (ffmpeg) have no device implementation: the recipe still DRAWS them (so the
-    random stream matches the reference) but they are not applied - wind noise is mixed additively at its drawn SNR - and each
-    omission is counted in ``skipped``.  ``return_noise``: -> (speech, noisy, scaled noise), what the offline simulator stores under
-    ``--store_noise``."""
+    (ffmpeg) has no device implementation and the wind-noise side-chain compressor (ffmpeg) is off by default: the recipe still DRAWS
+    them (so the random stream matches the reference) but they are not applied - wind noise is mixed additively at its drawn SNR - and
+    each omission is counted in ``skipped``.  ``return_noise``: -> (speech, noisy, scaled noise), what the offline simulator stores under
+    ``--store_noise``.
+
+    ``wind_compressor=True`` (opt-in; ``cfg.wind_noise_compressor = "device"``, ``--wind_noise_compressor device``): a wind row goes through
+    ``mix_noise`` as above - which yields its aligned, SNR-scaled noise - and then through ``wind_noise`` (16-bit round trips, side-chain
+    compressor, amix, clipper; the clean target of a row without an RIR rescaled as the reference does), and is not counted in ``skipped``.
+    The compressor is a restatement of ffmpeg's filter from its published definition, not pinned against the binary."""
     ops.require_cuda(speech, noise_raw)
     B, L = speech.shape
     dev = speech.device
@@ -382,11 +422,21 @@ def simulate_recipes(speech, lens, noise_raw, noise_lens, rir, rir_lens, rir_ear
         rir[:, 0].add_(_f32([0.0 if n > 0 else 1.0 for n in rir_lens], dev))
         noisy = add_reverberation(speech, lens, rir, full)
         speech = add_reverberation(speech, lens, rir, early)
-    for r in recipes:
-        if r.get("wind"):
+    wind_rows = [b for b, r in enumerate(recipes) if r.get("wind")]
+    if not wind_compressor:
+        for _ in wind_rows:
             count("wind_noise")
-    noisy, noise = mix_noise(noisy, noise_raw, noise_lens, lens, [float(r["snr"]) for r in recipes],
+    x = noisy
+    noisy, noise = mix_noise(x, noise_raw, noise_lens, lens, [float(r["snr"]) for r in recipes],
                              torch.tensor([int(r.get("noise_offset", 0)) for r in recipes], dtype=torch.int32))
+    if wind_compressor and wind_rows:
+        for b in wind_rows:
+            if "wind_noise" not in recipes[b].get("params", {}):
+                raise KeyError("recipe %d is a wind row without params['wind_noise'] (parse_row(..., wind_compressor=True) fills it)" % b)
+        if speech.data_ptr() == x.data_ptr():
+            speech = speech.clone()                 # rows without an RIR get their clean target rescaled: never the caller's tensor
+        wind_noise(speech, x, noise, noisy, lens, wind_rows, [recipes[b]["params"]["wind_noise"] for b in wind_rows],
+                   [rir is not None and int(rir_lens[b]) > 0 for b in wind_rows], fs)
     todo = []
     for r in recipes:
         mine = []

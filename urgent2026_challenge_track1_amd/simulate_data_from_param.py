@@ -8,7 +8,8 @@ ragged batches under a sample budget and go through ``mixing.simulate_recipes`` 
 RIR / early-RIR convolution, noise tiling or cropping, SNR scaling, the augmentation chain, joint peak normalisation), are quantised to
 16 bit there, and ``.flac`` outputs are encoded there too (csrc/flac_enc.hip).  ``.wav`` outputs go through ``write_audio``.
 
-Flags: the generator's, plus ``--meta_tsv``, ``--nj``, ``--chunksize``, ``--highpass`` (:592-622) and ``--unsupported_augmentation``.
+Flags: the generator's, plus ``--meta_tsv``, ``--nj``, ``--chunksize``, ``--highpass`` (:592-622), ``--unsupported_augmentation`` and
+``--wind_noise_compressor``.
   * ``--highpass`` keeps the reference's ``type=bool``: ANY non-empty string is true, ``--highpass False`` included; only leaving the
     flag out (or ``--highpass ""``) switches the filter off.
   * The reference reads ``log_dir/meta.tsv`` and never opens ``--meta_tsv``; so does this module, and it refuses a ``--meta_tsv`` that
@@ -18,6 +19,9 @@ Flags: the generator's, plus ``--meta_tsv``, ``--nj``, ``--chunksize``, ``--high
     additively at its drawn SNR.  ``--unsupported_augmentation warn|raise|count`` (default warn; the trainer's semantics): ``raise``
     stops before anything is simulated, ``warn`` warns once, and every affected row is listed in ``log_dir/unsupported.tsv``
     (id, augmentation) under all three - a dataset on disk must say what it lacks.
+  * ``--wind_noise_compressor skip|device`` (default skip: the line above).  ``device``: a wind row is mixed by ``wind_noise()`` (:129-217) on
+    the device - 16-bit round trips, ffmpeg's ``sidechaincompress`` + ``amix`` restated from their published definition (not pinned against
+    the binary), the clipper - and is no longer listed as lacking.
 """
 import ast
 import os
@@ -45,6 +49,9 @@ def get_parser():
                    help="Apply highpass filter to source speech (type=bool as in the reference: any non-empty string is true)")
     g.add_argument("--unsupported_augmentation", choices=("warn", "raise", "count"), default="warn",
                    help="what to do with rows whose codec / wind-noise compressor the device simulator does not apply")
+    g.add_argument("--wind_noise_compressor", choices=("skip", "device"), default="skip",
+                   help="skip: wind noise is mixed additively and the row listed as lacking; device: the side-chain compressor recipe "
+                        "runs on the device (ffmpeg's filter restated, not pinned against the binary)")
     return parser
 
 
@@ -84,15 +91,25 @@ def noise_offset(uid, len_speech, len_noise):
     return int(np.random.default_rng(int(uid.split("_")[-1])).integers(0, abs(len_speech - len_noise)))
 
 
-def parse_row(info, highpass):
-    """a meta.tsv row -> the recipe ``mixing.simulate_recipes`` takes, and the augmentations it will not apply"""
+WIND_FIELDS = ("threshold", "ratio", "attack", "release", "sc_gain", "clipping", "clipping_threshold")
+
+
+def parse_row(info, highpass, wind_compressor=False):
+    """a meta.tsv row -> the recipe ``mixing.simulate_recipes`` takes, and the augmentations it will not apply.  ``wind_compressor``: the
+    seven fields of a wind row's ``wind_noise(...)`` text go to ``params["wind_noise"]`` (:494-518; ``clipping`` as the reference evaluates it,
+    ``bool(text)``: true for "False" too) and the row is not listed as lacking."""
     params, order, unsupported = {}, [], []
     wind = info["noise_uid"].startswith("wind_noise")
     parts = info["augmentation"].split("/")
     if wind:
-        assert len([a for a in parts if a.startswith("wind_noise")]) == 1, \
-            "Configuration for the wind-noise simulation is necessary: %s %s" % (parts, info["noise_uid"])
-        unsupported.append("wind_noise")
+        mine = [a for a in parts if a.startswith("wind_noise")]
+        assert len(mine) == 1, "Configuration for the wind-noise simulation is necessary: %s %s" % (parts, info["noise_uid"])
+        if wind_compressor:
+            vals = re.fullmatch(r"wind_noise\(threshold=(.*),ratio=(.*),attack=(.*),release=(.*),sc_gain=(.*),clipping=(.*),"
+                                r"clipping_threshold=(.*)\)", mine[0]).groups()
+            params["wind_noise"] = {k: bool(v) if k == "clipping" else float(v) for k, v in zip(WIND_FIELDS, vals)}
+        else:
+            unsupported.append("wind_noise")
     for a in parts:
         if a in ("none", "") or a.startswith("wind_noise"):
             continue
@@ -169,7 +186,7 @@ def load_item(info, recipe, speech_dic, noise_dic, rir_dic):
                 rir_fs=int(rir_fs))
 
 
-def simulate_items(items, device, skipped=None):
+def simulate_items(items, device, skipped=None, wind_compressor=False):
     """items of one fs -> (clean, noisy, noise) f32 [B, T] on the device, lengths"""
     import torch
     from .dataset import RawMixBatch
@@ -180,7 +197,7 @@ def simulate_items(items, device, skipped=None):
             x = torch.as_tensor(it["speech"], dtype=torch.float32).to(device)
             it["speech"] = resample_soxr_hq(x, it["speech_fs"], fs)[:, :it["length"]].cpu().numpy()
     batch = RawMixBatch(items)
-    clean, noisy, noise = batch.simulate(device, skipped, return_noise=True)
+    clean, noisy, noise = batch.simulate(device, skipped, return_noise=True, wind_compressor=wind_compressor)
     return clean, noisy, noise, batch.lengths
 
 
@@ -222,13 +239,15 @@ def run(args, device="cuda"):
     noise_dic.update(read_flat_scps(args.wind_noise_scps))
     rir_dic = read_flat_scps(args.rir_scps)
     rows = read_meta(args.log_dir)
-    parsed = [parse_row(r, args.highpass) for r in rows]
+    wind_compressor = getattr(args, "wind_noise_compressor", "skip") == "device"
+    parsed = [parse_row(r, args.highpass, wind_compressor) for r in rows]
     lacking = [(r["id"], a) for r, (_, un) in zip(rows, parsed) for a in un]
     policy = args.unsupported_augmentation
     if lacking:
-        msg = ("%d row(s) of meta.tsv carry an augmentation the device simulator does not apply (%s): it is skipped for that row (wind "
-               "noise is mixed additively at its drawn SNR); the rows are listed in %s (--unsupported_augmentation warn | raise | count)"
-               % (len({i for i, _ in lacking}), sorted({a for _, a in lacking}), Path(args.log_dir) / "unsupported.tsv"))
+        msg = ("%d row(s) of meta.tsv carry an augmentation the device simulator does not apply (%s): it is skipped for that row%s; "
+               "the rows are listed in %s (--unsupported_augmentation warn | raise | count)"
+               % (len({i for i, _ in lacking}), sorted({a for _, a in lacking}),
+                  "" if wind_compressor else " (wind noise is mixed additively at its drawn SNR)", Path(args.log_dir) / "unsupported.tsv"))
         if policy == "raise":
             raise NotImplementedError(msg)
         if policy == "warn":
@@ -246,7 +265,7 @@ def run(args, device="cuda"):
                 if it["length"] != int(rows[i]["length"]):
                     raise AssertionError("%s: the speech has %d samples at %d Hz, meta.tsv says length %s"
                                          % (rows[i]["id"], it["length"], it["fs"], rows[i]["length"]))
-            clean, noisy, noise, lens = simulate_items(items, device, skipped)
+            clean, noisy, noise, lens = simulate_items(items, device, skipped, wind_compressor)
             fs = items[0]["fs"]
             write_batch(clean, lens, fs, [rows[i]["clean_path"] for i in members], pool)
             write_batch(noisy, lens, fs, [rows[i]["noisy_path"] for i in members], pool)

@@ -78,10 +78,18 @@ def load_model_state(model, state_dict, with_ema=True):
     model.se_model.load_state_dict(sd)
 
 
-def to_device(batch, dev, skipped=None):
+def wind_compressor_on(cfg):
+    """cfg.wind_noise_compressor: "skip" (default: wind noise is mixed additively and counted as not applied) | "device" """
+    mode = getattr(cfg, "wind_noise_compressor", "skip")
+    if mode not in ("skip", "device"):
+        raise ValueError("wind_noise_compressor = %r: \"skip\" or \"device\"" % (mode,))
+    return mode == "device"
+
+
+def to_device(batch, dev, skipped=None, wind_compressor=False):
     """host batch -> device batch; a dynamic-mixing batch is SIMULATED here, on the device (mixing.simulate_recipes)."""
     if isinstance(batch, RawMixBatch):
-        return batch.materialise(dev, skipped)
+        return batch.materialise(dev, skipped, wind_compressor)
     clean, noisy, fs, lens = batch
     return clean.to(dev, non_blocking=True), noisy.to(dev, non_blocking=True), fs, lens
 
@@ -91,11 +99,17 @@ class DevicePrefetcher:
     its simulator kernels run beside the train step of batch i (whose recurrences leave most issue slots idle) instead of in front
     of step i+1.  The consumer's stream waits on the batch's event; the tensors are handed over with ``record_stream``."""
 
-    def __init__(self, loader, dev, skipped=None, depth=None):
+    def __init__(self, loader, dev, skipped=None, depth=None, wind_compressor=None):
         """``depth`` batches are staged ahead (2: the simulation of batch i + 2 may start as soon as step i - 1 is done, so a simulation
         that the low stream priority stretches past one step does not stall the next one)."""
         depth = int(os.environ.get("URSE_PREFETCH_DEPTH", "2")) if depth is None else int(depth)
         self.loader, self.dev, self.skipped, self.depth = loader, dev, skipped, max(1, depth)
+        # wind rows through the compressor recipe: cfg.wind_noise_compressor == "device" (train_se.fit passes it); a caller that passes nothing
+        # (bench.py --dynamic-mix) gets the configuration's default, which URSE_WIND_NOISE_COMPRESSOR=device overrides for a measurement
+        if wind_compressor is None:
+            env = os.environ.get("URSE_WIND_NOISE_COMPRESSOR")
+            wind_compressor = wind_compressor_on(Config(wind_noise_compressor=env) if env else Config())
+        self.wind_compressor = bool(wind_compressor)
         # lowest HIP priority: the simulator's thousands of small workgroups only take CUs the train step leaves idle, so they cannot
         # keep a workgroup of a cooperative recurrence kernel (which spins on its peers) off its CU (ADVICE r2)
         self.stream = ops.low_priority_stream(dev, force=True) if torch.device(dev).type == "cuda" else None
@@ -104,10 +118,10 @@ class DevicePrefetcher:
         if isinstance(batch, RawMixBatch):
             ops.PREFETCH_RESERVED_CUS = 8          # simulator kernels beside the step: the cooperative forward leaves them CUs (ops.py)
         if self.stream is None:
-            return to_device(batch, self.dev, self.skipped), None
+            return to_device(batch, self.dev, self.skipped, self.wind_compressor), None
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))      # buffers freed by the consumer are safe to reuse
         with torch.cuda.stream(self.stream):
-            out = to_device(batch, self.dev, self.skipped)
+            out = to_device(batch, self.dev, self.skipped, self.wind_compressor)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return out, ev
@@ -228,10 +242,11 @@ def fit(cfg, max_steps=None, log_every=50):
     t0 = time.time()
     skipped = {}                                # augmentations the recipes drew but the device path cannot apply
     policy, warned = getattr(cfg, "unsupported_augmentation", "warn"), False
+    wind_compressor = wind_compressor_on(cfg)
     for epoch in range(epoch0, cfg.num_train_epochs):
         # the reference never advances the sampler epoch (quirk C.3: on_train_epoch_start is not a DataModule hook)
         n_batches, in_epoch = equalise_batch_counts(dm.train_batch_sampler, world, dev), 0
-        for batch in DevicePrefetcher(train_loader, dev, skipped):
+        for batch in DevicePrefetcher(train_loader, dev, skipped, wind_compressor=wind_compressor):
             loss = model.training_step(batch)
             loss.backward()
             model.optimizer_step(opt, reducer)
