@@ -391,6 +391,9 @@ class BSRNNCore(nn.Module):
         f0 = xoff = poff = 0
         K = 0
         for k, sb in enumerate(self.subbands):
+            if 2 * sb > 128:
+                raise ValueError("band %d is %d bins wide: the band split's affine backward covers one (re, im) column per thread of "
+                                 "its 128-thread blocks, 64 bins at the most" % (k, sb))
             xpad, ppad = ops.kpad(2 * sb, dtype), ops.kpad(4 * sb, dtype)
             rows.append([f0, sb, xoff, xpad, 2 * f0, poff, ppad, 0])
             for f in range(f0, min(F, f0 + sb)):

@@ -209,6 +209,8 @@ extern "C" int urse_bandsplit_norm_bwd(const float* spec, const float* dxnb, con
                                        void* stream) {
   URSE_CHECK_ARG(spec && dxnb && bands && stats && dgamma && dbeta, "urse_bandsplit_norm_bwd: null pointer");
   const int tchunk = 64;
+  // 128 threads = one per (re, im) column of a band: a band wider than 64 bins would lose the columns c >= 128 without a sign.
+  // The widest band of either table is 60 bins; BSRNNCore._band_tables refuses a wider one.
   hipLaunchKernelGGL(bandsplit_bwd_affine_kernel, dim3(K, B, ceil_div(T, tchunk)), dim3(128), 0, (hipStream_t)stream,
                      spec, dxnb, (const Band*)bands, stats, dgamma, dbeta, T, F, ldx, eps, tchunk);
   URSE_CHECK_LAUNCH("urse_bandsplit_norm_bwd");
