@@ -164,6 +164,25 @@ int urse_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* 
 /* 1 if the URSE_BF16_ACT_F16 form of urse_gemm_tn (No2 == 0; the wide-and-short fc gradient, needs colsum) / urse_gemm_tn_dual (No2 > 0) serves
  * the shape - `d_model.py:61-89`'s backward in an f16-forward step (nn.Linear / nn.LSTM weight gradients, `bsrnn_flowse.py:296-307`). */
 int urse_gemm_tn_act_f16_supported(int64_t R, int64_t Mo, int64_t No, int64_t No2, int with_colsum, int64_t inner, int64_t period);
+/* The launch urse_gemm_tn (No2 == 0) / urse_gemm_tn_dual (No2 > 0) makes of these arguments, from the function both launch by; no GPU is touched.
+ * plan[URSE_TN_PLAN_FIELDS] = {form (URSE_TN_FORM_*), the URSE_KV_* slot the launch counts in (-1: none of its own), 1 if it is the mixed-operand
+ * instance (counted in URSE_KV_TN_ACT_F16 too), column tiles per wave (7 / 8) and column-sum mode (0 none, 1 of A, 2 of the transposed problem's B)
+ * of the ring kernel (0 and -1 on the other forms), output tiles, split-R slices, rows_per_slice, grid = tiles * slices}.
+ * Like urse_gemm_tn_act_f16_supported it assumes what it cannot see: 16-byte aligned operands and row pitches, and leading dimensions that
+ * suffice (lda >= Mo, ldb >= round_up(No, 8), ldb2 >= No2); urse_gemm_tn_dual makes two single launches, or its ring kernel, of a call without them.
+ * URSE_TN_FORM_TWO_SINGLE: ask again with No2 = 0 for each half (the first with shift 0, inner 1, period 0; the second without column sums).
+ * URSE_TN_FORM_NONE (URSE_BF16_ACT_F16 only; the call would return URSE_ERR_UNSUPPORTED) is URSE_OK here, with the other fields as on no launch.
+ * URSE_ERR_INVALID_ARG: a size that is not positive (No2 < 0), target_workgroups < 0, plan == NULL. */
+#define URSE_TN_FORM_NONE 0        /* mixed operands: no kernel */
+#define URSE_TN_FORM_128 1         /* gemm_tn_kernel, 128 x 128 tiles */
+#define URSE_TN_FORM_RING 2        /* gemm_tn_dma_kernel */
+#define URSE_TN_FORM_RING_T 3      /* gemm_tn_dma_kernel on the transposed problem */
+#define URSE_TN_FORM_DUAL224 4     /* gemm_tn_dual224_kernel, 224 x 320 tiles over [B | B2 | ones] */
+#define URSE_TN_FORM_DUAL_RING 5   /* gemm_tn_dma_kernel over the column tiles of B, then of B2 */
+#define URSE_TN_FORM_TWO_SINGLE 6  /* urse_gemm_tn_dual as two urse_gemm_tn calls */
+#define URSE_TN_PLAN_FIELDS 9
+int urse_gemm_tn_plan(int64_t R, int64_t Mo, int64_t No, int64_t No2, int with_colsum, int64_t shift, int64_t inner,
+                      int64_t period, int64_t invalid_step, int64_t perm_h, int dtype, int target_workgroups, int64_t* plan);
 /* Two weight gradients that share their A operand in one pass over A (the two wgrads of one LSTM direction):
  * C[Mo,No] += A^T B (+ colsum) and C2[Mo,No2] += A^T B2', B2' = B2 shifted / masked as in urse_gemm_tn. */
 int urse_gemm_tn_dual(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* colsum,

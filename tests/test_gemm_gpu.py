@@ -466,3 +466,34 @@ def test_gemm_tn_mixed_operands_refuse_shapes_without_a_kernel(lib):
     assert not ops.tn_act_f16_supported(64, 224, 64, 0, True)
     with pytest.raises(UrseError):
         ops.gemm_tn(A, Bm, torch.zeros(224, 64, device="cuda"), Mo=224, No=64)
+
+
+@pytest.mark.parametrize("kind", ["tn_128", "tn_ring", "tn_ring_perm", "tn_dual224", "tn_dual224_act_f16", "tn_fc_act_f16"])
+def test_gemm_tn_launch_counts_where_the_plan_says(lib, kind):
+    """ops.gemm_tn_plan names the launch_counts() slot of the launch the same arguments make (the shapes of the poison test above and of the fc
+    gradient against f16 h; zero operands, one launch each - the numerics are the other tests')."""
+    from urgent2026_challenge_track1_amd import ops
+    bf, mixed = torch.bfloat16, kind.endswith("act_f16")
+    z = lambda r, c, dt: torch.zeros(r, c, dtype=dt, device="cuda")
+    if kind.startswith("tn_dual224"):
+        R, H, N, inner, period = 34 * 32 * 16, 392, 196, 34, 32
+        act = torch.float16 if mixed else bf
+        A, X, Hh = z(R, 4 * H, bf), z(R, 224, act), z(R, 416, act)
+        kw = dict(shift=-inner, inner=inner, period=period, invalid_step=0, perm_h=H)
+        plan = ops.gemm_tn_plan(R, 4 * H, N, H, dtype=ops._tn_dt(A, X, Hh), **kw)
+        ops.launch_counts(reset=True)
+        ops.gemm_tn_dual(A, X, z(4 * H, N, torch.float32), torch.zeros(4 * H, device="cuda"), Hh, z(4 * H, H, torch.float32), 4 * H, N, H,
+                         kw["shift"], inner, period, 0, perm_h=H)
+    else:
+        R, Mo, No, kw, dt, bdt = {"tn_128": (333, 200, 40, {}, torch.float32, torch.float32), "tn_ring": (20000, 608, 200, {}, bf, bf),
+                                  "tn_ring_perm": (34 * 500 + 7, 1568, 392, dict(shift=-1, inner=1, period=34, invalid_step=0, perm_h=392), bf, bf),
+                                  "tn_fc_act_f16": (34 * 640, 196, 784, {}, bf, torch.float16)}[kind]
+        A, Bm = z(R, (Mo + 31) // 32 * 32, dt), z(R, (No + 31) // 32 * 32, bdt)
+        plan = ops.gemm_tn_plan(R, Mo, No, dtype=ops._tn_dt(A, Bm), **kw)
+        ops.launch_counts(reset=True)
+        ops.gemm_tn(A, Bm, z(Mo, No, torch.float32), colsum=torch.zeros(Mo, device="cuda"), Mo=Mo, No=No, **kw)
+    counts = ops.launch_counts()
+    assert plan["form"] == {"tn_128": "tn_128", "tn_ring": "ring", "tn_ring_perm": "ring", "tn_fc_act_f16": "ring_t"}.get(kind, "dual224"), plan
+    assert plan["act_f16"] == mixed and counts["tn_act_f16"] == int(mixed), (plan, counts)
+    assert {k: v for k, v in counts.items() if v and k != "tn_act_f16"} == {plan["slot"]: 1}, (plan, counts)
+    torch.cuda.synchronize()

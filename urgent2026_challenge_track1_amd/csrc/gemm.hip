@@ -2349,91 +2349,119 @@ extern "C" int urse_gemm_nt_grouped_h(const void* descs, const int64_t* host_des
 // kernel on part of the chip (bsrnn.py: deferred wgrads next to the time path's BPTT) passes the CUs that are actually free,
 // so the launch is one round of long workgroups instead of two-and-a-bit rounds.  Per call: the library keeps no tuning state.
 
+// ---- the weight-gradient launch plan: which kernel, which grid.  urse_gemm_tn and urse_gemm_tn_dual launch what tn_plan says,
+// urse_gemm_tn_act_f16_supported and urse_gemm_tn_plan answer from the same function (no HIP call, no pointer read). ----
+struct TnPlanIn {
+  long R, Mo, No, No2, shift, inner, period, invalid_step, perm_h;       // No2 == 0: urse_gemm_tn, No2 > 0: urse_gemm_tn_dual
+  int dtype, target_workgroups;
+  bool colsum;
+  // what urse_gemm_tn_dual reads off its real arguments: A, B, B2 and their row pitches multiples of 16 bytes; lda >= Mo, ldb >= round_up(No, 8), ldb2 >= No2
+  bool aligned = true, lda_ok = true, ldb8_ok = true, ldb2_ok = true;
+};
+struct TnPlan {
+  int form = URSE_TN_FORM_NONE, kv = -1;                 // kv: the URSE_KV_* slot the launch notes (-1: this call launches nothing itself)
+  int act_f16 = 0;                                       // the mixed-operand instance (noted in URSE_KV_TN_ACT_F16 as well)
+  int ntw = 0, csm = -1;                                 // launch_tn_dma's column tiles per wave and column-sum mode (ring forms only)
+  long tiles = 0, slices = 0, rows_per_slice = 0, grid = 0;
+};
+
+// split-R: `target` workgroups over pl.tiles tiles -> slices -> rows per slice in whole `quantum` rows -> the slices that leaves
+static TnPlan tn_split_rows(TnPlan pl, long R, long target, long quantum, long max_slices = 0) {
+  long slices = target / pl.tiles;
+  if (max_slices > 0 && slices > max_slices) slices = max_slices;
+  if (slices < 1) slices = 1;
+  pl.rows_per_slice = ((R + slices - 1) / slices + quantum - 1) / quantum * quantum;
+  pl.slices = (R + pl.rows_per_slice - 1) / pl.rows_per_slice;
+  pl.grid = pl.tiles * pl.slices;
+  return pl;
+}
+
+static TnPlan tn_plan(const TnPlanIn& in) {
+  static const bool no_dma = getenv("URSE_TN_NO_DMA") != nullptr, no224 = getenv("URSE_TN_NO_224") != nullptr;
+  TnPlan pl;
+  const bool act_f16 = in.dtype == URSE_BF16_ACT_F16;    // A = bf16 gradients, B / B2 = the forward's f16 activations (converted in registers)
+  const bool bf16 = act_f16 || in.dtype == URSE_BF16;
+  const long target = in.target_workgroups > 0 ? in.target_workgroups : 256;
+  const long inner = in.inner > 0 ? in.inner : 1;
+  const long R = in.R, Mo = in.Mo, No = in.No, No2 = in.No2;
+  const bool ring_rows = bf16 && !no_dma && R >= 16384 && R < (1L << 30);
+  const bool mask_fits = inner < (1L << 31) && in.shift > -(1L << 30) && in.shift < (1L << 30) && in.period < (1L << 31);
+  auto ring = [&](int form, int kv, long rows, long cols, int csm) {       // 256 x (32 * ntw) tiles on the LDS-DMA ring, one workgroup per CU
+    pl.form = form; pl.kv = kv; pl.csm = csm;
+    pl.ntw = (cols + 223) / 224 * 224 < (cols + 255) / 256 * 256 ? 7 : 8;
+    pl.tiles = ((rows + 255) / 256) * ((cols + 32L * pl.ntw - 1) / (32L * pl.ntw));
+    return tn_split_rows(pl, R, target, 32);
+  };
+  if (No2 == 0) {
+    if (ring_rows && in.perm_h == 0 && in.shift == 0 && in.period == 0 && Mo < 512 && Mo >= 160 && No >= 512) {
+      // wide-and-short gradient (fc weight [196, 784]): the ring kernel on the transposed problem.  Its one mixed instance is <7, 2>.
+      pl.act_f16 = act_f16;
+      const TnPlan t = ring(URSE_TN_FORM_RING_T, URSE_KV_TN_RING_T, No, Mo, in.colsum ? 2 : 0);
+      return act_f16 && !(in.colsum && t.ntw == 7) ? TnPlan() : t;
+    }
+    if (act_f16) return pl;
+    if (ring_rows && Mo >= 512 && No >= 160 && mask_fits) return ring(URSE_TN_FORM_RING, URSE_KV_TN_RING, Mo, No, in.colsum ? 1 : 0);      // big weight gradients
+    pl.form = URSE_TN_FORM_128; pl.kv = URSE_KV_TN_128;
+    pl.tiles = ((Mo + BM - 1) / BM) * ((No + BN - 1) / BN);
+    // one full round of resident workgroups (3 per CU at this kernel's register budget): a partial second round costs
+    // up to 25 % on the big weight-gradient shapes
+    const char* e = getenv("URSE_TN_TARGET");
+    const long bkr = bf16 ? 32 : 16;
+    return tn_split_rows(pl, R, e ? atol(e) : 768, bkr, (R + 4 * bkr - 1) / (4 * bkr));
+  }
+  if (!(ring_rows && Mo >= 512 && mask_fits && in.aligned)) {
+    if (!act_f16) pl.form = URSE_TN_FORM_TWO_SINGLE;     // the caller plans each half with No2 = 0
+    return pl;
+  }
+  // 224 x 320 tiles over the virtual operand [B | B2 | ones] when the rows are whole 224-row tiles, the columns fit two tiles and the
+  // shifted operand's step mask covers the rows the shift reaches (whole sequences of `period` steps, shift = -/+ inner)
+  const long V = ((No + 7) & ~7L) + No2 + (in.colsum ? 1 : 0), tl224 = (Mo / 224) * ((V + 319) / 320);
+  const bool mask_covers_range = in.period > 0 && R % (inner * in.period) == 0 &&
+                                 ((in.shift == -inner && in.invalid_step == 0) || (in.shift == inner && in.invalid_step == in.period - 1));
+  if (!no224 && Mo % 224 == 0 && No2 % 8 == 0 && in.ldb2_ok && R % 32 == 0 && mask_covers_range && V <= 640 && in.ldb8_ok &&
+      in.perm_h >= 0 && in.lda_ok && tl224 <= target && !(act_f16 && tl224 > 256)) {
+    pl.form = URSE_TN_FORM_DUAL224; pl.kv = URSE_KV_TN_DUAL; pl.act_f16 = act_f16;
+    pl.tiles = tl224;
+    return tn_split_rows(pl, R, target, 32);
+  }
+  if (act_f16) return pl;                                // (the ring kernel has no mixed dual instance)
+  pl.form = URSE_TN_FORM_DUAL_RING; pl.kv = URSE_KV_TN_DUAL; pl.ntw = 7; pl.csm = in.colsum ? 1 : 0;      // 7 column tiles per wave: 196 -> 224, 392 -> 448
+  pl.tiles = ((Mo + 255) / 256) * ((No + 223) / 224 + (No2 + 223) / 224);
+  return tn_split_rows(pl, R, target, 32);
+}
+
 extern "C" int urse_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,
                             float* colsum, int64_t R, int64_t Mo, int64_t No, int64_t shift, int64_t inner,
                             int64_t period, int64_t invalid_step, int64_t perm_h, int dtype, int target_workgroups,
                             void* stream) {
   URSE_CHECK_ARG(A && B && C && R > 0 && Mo > 0 && No > 0 && target_workgroups >= 0, "urse_gemm_tn: bad argument");
-  const long g_tn_target_wgs = target_workgroups > 0 ? target_workgroups : 256;
-  const bool act_f16 = dtype == URSE_BF16_ACT_F16;       // A = bf16 gradients, B = the forward's f16 activations (converted in registers)
-  if (act_f16) {
-    if (!urse_gemm_tn_act_f16_supported(R, Mo, No, 0, colsum != nullptr, 1, 0) || perm_h != 0 || shift != 0 || period != 0) {
-      set_error("urse_gemm_tn: URSE_BF16_ACT_F16 serves the shapes urse_gemm_tn_act_f16_supported accepts (R%ld Mo%ld No%ld)", (long)R, (long)Mo, (long)No);
-      return URSE_ERR_UNSUPPORTED;
-    }
-    dtype = URSE_BF16;
+  const TnPlan pl = tn_plan({R, Mo, No, 0, shift, inner, period, invalid_step, perm_h, dtype, target_workgroups, colsum != nullptr});
+  if (pl.form == URSE_TN_FORM_NONE) {
+    set_error("urse_gemm_tn: URSE_BF16_ACT_F16 serves the shapes urse_gemm_tn_act_f16_supported accepts (R%ld Mo%ld No%ld)", (long)R, (long)Mo, (long)No);
+    return URSE_ERR_UNSUPPORTED;
   }
-  const int es = dtype == URSE_BF16 ? 2 : 4;
+  const bool bf16 = dtype == URSE_BF16 || dtype == URSE_BF16_ACT_F16;
+  const int es = bf16 ? 2 : 4;
   URSE_CHECK_ARG((lda * es) % 16 == 0 && (ldb * es) % 16 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0,
                  "urse_gemm_tn: operands must be 16-byte aligned with 16-byte-multiple row pitch");
   URSE_CHECK_ARG(lda >= Mo && ldb >= No && ldc >= No, "urse_gemm_tn: leading dimension too small");
+  URSE_CHECK_ARG(pl.grid < (1L << 31), "urse_gemm_tn: too many tiles");
   TnArgs p;
   p.A = (const char*)A; p.B = (const char*)B; p.C = C; p.colsum = colsum;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.R = R; p.Mo = Mo; p.No = No;
-  p.shift = shift; p.inner = inner > 0 ? inner : 1; p.period = period; p.invalid_step = invalid_step;
-  p.perm_h = perm_h;
+  p.shift = shift; p.inner = inner > 0 ? inner : 1; p.period = period; p.invalid_step = invalid_step; p.perm_h = perm_h;
   p.B2 = nullptr; p.C2 = nullptr; p.ldb2 = p.ldc2 = p.No2 = p.nt1 = 0; p.pad_[0] = p.pad_[1] = 0;
-  static const bool no_dma = getenv("URSE_TN_NO_DMA") != nullptr;
-  if (dtype == URSE_BF16 && !no_dma && perm_h == 0 && shift == 0 && period == 0 && Mo < 512 && Mo >= 160 && No >= 512 &&
-      R >= 16384 && R < (1L << 30)) {
-    // wide-and-short gradient (fc weight [196, 784]): run the big kernel on the transposed problem
-    TnArgs q = p;
-    q.A = (const char*)B; q.lda = ldb; q.Mo = No;
-    q.B = (const char*)A; q.ldb = lda; q.No = Mo;
-    q.perm_h = TN_TRANSPOSED;
-    const long pad7 = (q.No + 223) / 224 * 224, pad8 = (q.No + 255) / 256 * 256;
-    const int ntw = pad7 < pad8 ? 7 : 8;
-    const long bnx = 32L * ntw;
-    const long tl = ((q.Mo + 255) / 256) * ((q.No + bnx - 1) / bnx);
-    long slices = g_tn_target_wgs / tl;
-    if (slices < 1) slices = 1;
-    long rps = (R + slices - 1) / slices;
-    rps = (rps + 31) / 32 * 32;
-    slices = (R + rps - 1) / rps;
-    q.rows_per_slice = rps;
-    dim3 grid((unsigned)(tl * slices));
-    note_launch(URSE_KV_TN_RING_T);
-    if (act_f16) note_launch(URSE_KV_TN_ACT_F16);
-    launch_tn_dma(ntw, colsum ? 2 : 0, grid, (hipStream_t)stream, q, act_f16 ? 1 : 0);
-    URSE_CHECK_LAUNCH("urse_gemm_tn");
-    return URSE_OK;
+  p.rows_per_slice = pl.rows_per_slice;
+  if (pl.form == URSE_TN_FORM_RING_T) {                  // the ring kernel on the transposed problem
+    p.A = (const char*)B; p.lda = ldb; p.Mo = No;
+    p.B = (const char*)A; p.ldb = lda; p.No = Mo;
+    p.perm_h = TN_TRANSPOSED;
   }
-  if (dtype == URSE_BF16 && !no_dma && Mo >= 512 && No >= 160 && R >= 16384 && inner < (1L << 31) && R < (1L << 30) && shift > -(1L << 30) && shift < (1L << 30) && period < (1L << 31)) {
-    // big weight gradients: 256-wide tiles on the LDS-DMA ring, one workgroup per CU
-    const long pad7 = (No + 223) / 224 * 224, pad8 = (No + 255) / 256 * 256;
-    const int ntw = pad7 < pad8 ? 7 : 8;
-    const long bnx = 32L * ntw;
-    const long tl = ((Mo + 255) / 256) * ((No + bnx - 1) / bnx);
-    long slices = g_tn_target_wgs / tl;
-    if (slices < 1) slices = 1;
-    long rps = (R + slices - 1) / slices;
-    rps = (rps + 31) / 32 * 32;
-    slices = (R + rps - 1) / rps;
-    p.rows_per_slice = rps;
-    dim3 grid((unsigned)(tl * slices));
-    note_launch(URSE_KV_TN_RING);
-    launch_tn_dma(ntw, colsum ? 1 : 0, grid, (hipStream_t)stream, p);
-    URSE_CHECK_LAUNCH("urse_gemm_tn");
-    return URSE_OK;
-  }
-  const long tiles = ((Mo + BM - 1) / BM) * ((No + BN - 1) / BN);
-  const int bkr = dtype == URSE_BF16 ? 32 : 16;
-  // one full round of resident workgroups (3 per CU at this kernel's register budget): a partial second round costs
-  // up to 25 % on the big weight-gradient shapes
-  long target = 768;
-  if (const char* e = getenv("URSE_TN_TARGET")) target = atol(e);
-  long slices = target / tiles;
-  const long max_slices = (R + 4 * bkr - 1) / (4 * bkr);
-  if (slices > max_slices) slices = max_slices;
-  if (slices < 1) slices = 1;
-  long rps = (R + slices - 1) / slices;
-  rps = (rps + bkr - 1) / bkr * bkr;
-  slices = (R + rps - 1) / rps;
-  p.rows_per_slice = rps;
-  URSE_CHECK_ARG(tiles * slices < (1L << 31), "urse_gemm_tn: too many tiles");
-  dim3 grid((unsigned)(tiles * slices));
-  note_launch(URSE_KV_TN_128);
-  if (dtype == URSE_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)pl.grid);
+  note_launch(pl.kv);
+  if (pl.act_f16) note_launch(URSE_KV_TN_ACT_F16);
+  if (pl.form != URSE_TN_FORM_128) launch_tn_dma(pl.ntw, pl.csm, grid, (hipStream_t)stream, p, pl.act_f16);
+  else if (bf16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p);
   URSE_CHECK_LAUNCH("urse_gemm_tn");
   return URSE_OK;
@@ -2454,17 +2482,22 @@ extern "C" int urse_gemm_tn_grouped(const void* descs, int groups, int max_block
 // which weight-gradient shapes have a mixed-operand (URSE_BF16_ACT_F16) kernel: No2 == 0: urse_gemm_tn's transposed ring kernel with column sums
 // (the fc gradient [196, 784]); No2 > 0: urse_gemm_tn_dual's 224 x 320 kernel (row / mask conditions are checked by the call itself)
 extern "C" int urse_gemm_tn_act_f16_supported(int64_t R, int64_t Mo, int64_t No, int64_t No2, int with_colsum, int64_t inner, int64_t period) {
-  static const bool no_dma = getenv("URSE_TN_NO_DMA") != nullptr, no224 = getenv("URSE_TN_NO_224") != nullptr;
-  if (no_dma || R < 16384 || R >= (1L << 30)) return 0;
-  if (No2 == 0) {
-    const long pad7 = (Mo + 223) / 224 * 224, pad8 = (Mo + 255) / 256 * 256;        // (transposed: the kernel's column tiles run over Mo)
-    return (with_colsum && Mo < 512 && Mo >= 160 && No >= 512 && pad7 < pad8) ? 1 : 0;
-  }
-  const long No8 = (No + 7) & ~7L, V = No8 + No2 + (with_colsum ? 1 : 0);
+  // What the query takes for granted about the call it answers for (the forward drops its bf16 copies on this answer, the backward's
+  // call has to match it): target_workgroups 0 (256 workgroups), 16-byte aligned operands with sufficient leading dimensions, no row
+  // permutation, and the canonical step mask - urse_gemm_tn (No2 == 0): none (shift 0, period 0, whatever inner / period say here);
+  // urse_gemm_tn_dual: shift = -inner with invalid_step = 0 (shift = +inner with invalid_step = period - 1 plans the same).
   if (inner < 1) inner = 1;
-  // (the shifted operand's step mask must cover the rows the shift reaches: whole sequences of `period` steps, shift = -/+ inner)
-  return (!no224 && Mo >= 512 && Mo % 224 == 0 && No2 % 8 == 0 && R % 32 == 0 && V <= 640 && period > 0 && period < (1L << 31) && inner < (1L << 31) &&
-          R % (inner * period) == 0 && (Mo / 224) * ((V + 319) / 320) <= 256) ? 1 : 0;
+  if (No2 == 0) return tn_plan({R, Mo, No, 0, 0, 1, 0, 0, 0, URSE_BF16_ACT_F16, 0, with_colsum != 0}).act_f16;
+  return tn_plan({R, Mo, No, No2, -inner, inner, period, 0, 0, URSE_BF16_ACT_F16, 0, with_colsum != 0}).act_f16;
+}
+
+extern "C" int urse_gemm_tn_plan(int64_t R, int64_t Mo, int64_t No, int64_t No2, int with_colsum, int64_t shift, int64_t inner,
+                                 int64_t period, int64_t invalid_step, int64_t perm_h, int dtype, int target_workgroups, int64_t* plan) {
+  URSE_CHECK_ARG(plan && R > 0 && Mo > 0 && No > 0 && No2 >= 0 && target_workgroups >= 0, "urse_gemm_tn_plan: bad argument");
+  const TnPlan pl = tn_plan({R, Mo, No, No2, shift, inner, period, invalid_step, perm_h, dtype, target_workgroups, with_colsum != 0});
+  const int64_t fields[URSE_TN_PLAN_FIELDS] = {pl.form, pl.kv, pl.act_f16, pl.ntw, pl.csm, pl.tiles, pl.slices, pl.rows_per_slice, pl.grid};
+  memcpy(plan, fields, sizeof(fields));
+  return URSE_OK;
 }
 
 // dW1[Mo, No] += A^T B (+ colsum),  dW2[Mo, No2] += A^T B2' (B2' = B2 shifted / masked as in urse_gemm_tn) in ONE pass
@@ -2475,82 +2508,52 @@ extern "C" int urse_gemm_tn_dual(const void* A, int64_t lda, const void* B, int6
                                  int64_t perm_h, int dtype, int target_workgroups, void* stream) {
   URSE_CHECK_ARG(A && B && C && B2 && C2 && R > 0 && Mo > 0 && No > 0 && No2 > 0 && target_workgroups >= 0,
                  "urse_gemm_tn_dual: bad argument");
-  const long g_tn_target_wgs = target_workgroups > 0 ? target_workgroups : 256;
-  static const bool no_dma = getenv("URSE_TN_NO_DMA") != nullptr;
-  const bool act_f16 = dtype == URSE_BF16_ACT_F16;       // A = bf16 gradients, B / B2 = the forward's f16 activations
-  if (act_f16) {
-    if (!urse_gemm_tn_act_f16_supported(R, Mo, No, No2, colsum != nullptr, inner, period)) {
-      set_error("urse_gemm_tn_dual: URSE_BF16_ACT_F16 serves the shapes urse_gemm_tn_act_f16_supported accepts (R%ld Mo%ld No%ld No2%ld)", (long)R, (long)Mo, (long)No, (long)No2);
-      return URSE_ERR_UNSUPPORTED;
-    }
-    dtype = URSE_BF16;
-  }
-  const bool big = dtype == URSE_BF16 && !no_dma && Mo >= 512 && R >= 16384 && R < (1L << 30) && shift > -(1L << 30) && shift < (1L << 30) && period < (1L << 31) && inner < (1L << 31) &&
-                   (lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && (ldb2 * 2) % 16 == 0 && ((uintptr_t)A % 16) == 0 &&
-                   ((uintptr_t)B % 16) == 0 && ((uintptr_t)B2 % 16) == 0;
-  if (!big && act_f16) { set_error("urse_gemm_tn_dual: URSE_BF16_ACT_F16 needs 16-byte aligned operands"); return URSE_ERR_UNSUPPORTED; }
-  if (!big) {
+  TnPlanIn in{R, Mo, No, No2, shift, inner, period, invalid_step, perm_h, dtype, target_workgroups, colsum != nullptr};
+  in.aligned = (lda * 2) % 16 == 0 && (ldb * 2) % 16 == 0 && (ldb2 * 2) % 16 == 0 && ((uintptr_t)A % 16) == 0 &&
+               ((uintptr_t)B % 16) == 0 && ((uintptr_t)B2 % 16) == 0;
+  in.lda_ok = lda >= Mo; in.ldb8_ok = ldb >= ((No + 7) & ~7L); in.ldb2_ok = ldb2 >= No2;
+  const TnPlan pl = tn_plan(in);
+  if (pl.form == URSE_TN_FORM_TWO_SINGLE) {
     int rc = urse_gemm_tn(A, lda, B, ldb, C, ldc, colsum, R, Mo, No, 0, 1, 0, 0, perm_h, dtype, target_workgroups, stream);
     if (rc) return rc;
     return urse_gemm_tn(A, lda, B2, ldb2, C2, ldc2, nullptr, R, Mo, No2, shift, inner, period, invalid_step, perm_h, dtype,
                         target_workgroups, stream);
   }
   URSE_CHECK_ARG(lda >= Mo && ldb >= No && ldc >= No && ldb2 >= No2 && ldc2 >= No2, "urse_gemm_tn_dual: leading dimension too small");
+  if (pl.form == URSE_TN_FORM_NONE) {
+    set_error("urse_gemm_tn_dual: URSE_BF16_ACT_F16 needs 16-byte aligned operands and a shape, rows and step mask the 224 x 320 kernel takes at this "
+              "target (urse_gemm_tn_act_f16_supported; R%ld Mo%ld No%ld No2%ld)", (long)R, (long)Mo, (long)No, (long)No2);
+    return URSE_ERR_UNSUPPORTED;
+  }
   TnArgs p;
   p.A = (const char*)A; p.B = (const char*)B; p.C = C; p.colsum = colsum;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.R = R; p.Mo = Mo; p.No = No;
-  p.shift = shift; p.inner = inner > 0 ? inner : 1; p.period = period; p.invalid_step = invalid_step;
-  p.perm_h = perm_h;
+  p.shift = shift; p.inner = inner > 0 ? inner : 1; p.period = period; p.invalid_step = invalid_step; p.perm_h = perm_h;
   p.B2 = (const char*)B2; p.C2 = C2; p.ldb2 = ldb2; p.ldc2 = ldc2; p.No2 = No2; p.pad_[0] = p.pad_[1] = 0;
-  {
-    // 224 x 320 tiles over the virtual operand [B | B2 | ones] when the rows are whole 224-row tiles and the columns fit two tiles
-    static const bool no224 = getenv("URSE_TN_NO_224") != nullptr;
-    const long No8 = (No + 7) & ~7L, V = No8 + No2 + (colsum ? 1 : 0);
-    const bool mask_covers_range = period > 0 && R % ((inner > 0 ? inner : 1) * period) == 0 &&
-                                   ((shift == -(inner > 0 ? inner : 1) && invalid_step == 0) || (shift == (inner > 0 ? inner : 1) && invalid_step == period - 1));
-    if (!no224 && Mo % 224 == 0 && No2 % 8 == 0 && ldb2 >= No2 && R % 32 == 0 && mask_covers_range && V <= 640 && ldb >= No8 && perm_h >= 0 && lda >= Mo && ((Mo / 224) * ((V + 319) / 320)) <= g_tn_target_wgs) {
-      const long tl = (Mo / 224) * ((V + 319) / 320);
-      long slices = g_tn_target_wgs / tl;
-      if (slices < 1) slices = 1;
-      long rps = (R + slices - 1) / slices;
-      rps = (rps + 31) / 32 * 32;
-      slices = (R + rps - 1) / rps;
-      p.rows_per_slice = rps;
-      p.nt1 = 0;
-      {
-        // A/B switch, read per call: 2 = two stages per barrier with the queue drained (default), 3 = three stages in flight and one barrier per stage.
-        // Alone the deeper form is 2 % faster (profiles/r05_exp_tn224_depth_v1.log); in the train step it LOSES 2.1 ms, same box, both orders
-        // (130.38 / 130.73 against 132.91 / 132.47, profiles/r05_ab_tn224_depth_v3.log).  An earlier A/B had said the opposite - on a binary that held
-        // both loops in one kernel behind a run-time branch and spilled nine registers in either (see the template note at the kernel).
-        const char* e = getenv("URSE_TN224_DEPTH");
-        p.pad_[0] = e ? atol(e) : 2;
-      }
-      note_launch(URSE_KV_TN_DUAL);
-      if (act_f16) note_launch(URSE_KV_TN_ACT_F16);
-      if (act_f16) hipLaunchKernelGGL((gemm_tn_dual224_kernel<2, true>), dim3((unsigned)(tl * slices)), dim3(512), 0, (hipStream_t)stream, p);
+  p.rows_per_slice = pl.rows_per_slice;
+  const dim3 grid((unsigned)pl.grid);
+  note_launch(pl.kv);
+  if (pl.form == URSE_TN_FORM_DUAL_RING) {
+    p.nt1 = (No + 223) / 224;
+    launch_tn_dma(pl.ntw, pl.csm, grid, (hipStream_t)stream, p);
+  } else {
+    p.nt1 = 0;
+    // A/B switch, read per call: 2 = two stages per barrier with the queue drained (default), 3 = three stages in flight and one barrier per stage.
+    // Alone the deeper form is 2 % faster (profiles/r05_exp_tn224_depth_v1.log); in the train step it LOSES 2.1 ms, same box, both orders
+    // (130.38 / 130.73 against 132.91 / 132.47, profiles/r05_ab_tn224_depth_v3.log).  An earlier A/B had said the opposite - on a binary that held
+    // both loops in one kernel behind a run-time branch and spilled nine registers in either (see the template note at the kernel).
+    const char* e = getenv("URSE_TN224_DEPTH");
+    p.pad_[0] = e ? atol(e) : 2;
+    if (pl.act_f16) note_launch(URSE_KV_TN_ACT_F16);
+    if (pl.act_f16) hipLaunchKernelGGL((gemm_tn_dual224_kernel<2, true>), grid, dim3(512), 0, (hipStream_t)stream, p);
 #ifdef URSE_EXPERIMENTS      // (DMA issue between the MFMA groups, round 6: -8.5 % alone, neutral in the step, profiles/r06_ab_tn224_interleave_v1 / _v2.log - variant builds only)
-      else if (p.pad_[0] == 4) hipLaunchKernelGGL(gemm_tn_dual224_kernel<4>, dim3((unsigned)(tl * slices)), dim3(512), 0, (hipStream_t)stream, p);
+    else if (p.pad_[0] == 4) hipLaunchKernelGGL(gemm_tn_dual224_kernel<4>, grid, dim3(512), 0, (hipStream_t)stream, p);
 #endif
 #ifdef URSE_EXPERIMENTS      // (three stages in flight: +2 % alone, -2.1 ms LOST in the step, round 5 - variant builds only)
-      else if (p.pad_[0] == 3) hipLaunchKernelGGL(gemm_tn_dual224_kernel<3>, dim3((unsigned)(tl * slices)), dim3(512), 0, (hipStream_t)stream, p);
+    else if (p.pad_[0] == 3) hipLaunchKernelGGL(gemm_tn_dual224_kernel<3>, grid, dim3(512), 0, (hipStream_t)stream, p);
 #endif
-      else hipLaunchKernelGGL(gemm_tn_dual224_kernel<2>, dim3((unsigned)(tl * slices)), dim3(512), 0, (hipStream_t)stream, p);
-      URSE_CHECK_LAUNCH("urse_gemm_tn_dual");
-      return URSE_OK;
-    }
+    else hipLaunchKernelGGL(gemm_tn_dual224_kernel<2>, grid, dim3(512), 0, (hipStream_t)stream, p);
   }
-  if (act_f16) { set_error("urse_gemm_tn_dual: URSE_BF16_ACT_F16: rows / step mask outside what the 224 x 320 kernel takes"); return URSE_ERR_UNSUPPORTED; }
-  const long bnx = 224;                                   // 7 column tiles per wave: 196 -> 224, 392 -> 448
-  p.nt1 = (No + bnx - 1) / bnx;
-  const long tl = ((Mo + 255) / 256) * (p.nt1 + (No2 + bnx - 1) / bnx);
-  long slices = g_tn_target_wgs / tl;
-  if (slices < 1) slices = 1;
-  long rps = (R + slices - 1) / slices;
-  rps = (rps + 31) / 32 * 32;
-  slices = (R + rps - 1) / rps;
-  p.rows_per_slice = rps;
-  note_launch(URSE_KV_TN_DUAL);
-  launch_tn_dma(7, colsum ? 1 : 0, dim3((unsigned)(tl * slices)), (hipStream_t)stream, p);
   URSE_CHECK_LAUNCH("urse_gemm_tn_dual");
   return URSE_OK;
 }

@@ -206,6 +206,22 @@ def tn_act_f16_supported(R, Mo, No, No2=0, with_colsum=True, inner=1, period=0):
                                                                         int(inner), int(period)))
 
 
+TN_FORMS = ("none", "tn_128", "ring", "ring_t", "dual224", "dual_ring", "two_single")      # include/urse.h: URSE_TN_FORM_*
+TN_PLAN_FIELDS = ("form", "slot", "act_f16", "ntw", "colsum_mode", "tiles", "slices", "rows_per_slice", "grid")
+
+
+def gemm_tn_plan(R, Mo, No, No2=0, with_colsum=True, shift=0, inner=1, period=0, invalid_step=0, perm_h=0, dtype=BF16, target_wgs=0):
+    """the launch gemm_tn (No2 == 0) / gemm_tn_dual (No2 > 0) makes of these arguments, as a dict of TN_PLAN_FIELDS (urse_gemm_tn_plan: aligned
+    operands with sufficient leading dimensions assumed; no GPU needed).  form: one of TN_FORMS; slot: the launch_counts() name the launch counts
+    in (None: no launch of its own); dtype: a URSE_* code."""
+    import ctypes
+    plan = (ctypes.c_int64 * len(TN_PLAN_FIELDS))()
+    call("gemm_tn_plan", R, Mo, No, No2, int(bool(with_colsum)), shift, inner, period, invalid_step, perm_h, dtype, target_wgs, plan)
+    out = dict(zip(TN_PLAN_FIELDS, plan))
+    out.update(form=TN_FORMS[plan[0]], slot=None if plan[1] < 0 else KERNEL_VARIANTS[plan[1]], act_f16=bool(plan[2]))
+    return out
+
+
 def gemm_tn_dual(A, Bm, out, colsum, B2, out2, Mo, No, No2, shift, inner, period, invalid_step, perm_h=0, target_wgs=0):
     """out[Mo, No] += A^T Bm (+ colsum) and out2[Mo, No2] += A^T B2' (shifted / masked) in one pass over A."""
     require_cuda(A, Bm, B2, out, out2)
