@@ -6,7 +6,8 @@ TEST INFRASTRUCTURE - never imported by the product path.
 ``sdr_metric`` (:90-109) -> ``fast_bss_eval.bss_eval_sources(ref, inf, compute_permutation=False, clamp_db=50)``.
 Neither package is on disk: both are restated here from their published algorithms on numpy +
 ``scipy.signal.resample_poly`` (the routine pystoi itself calls).  Parity with the real packages: unpinned by the
-reference (no vectors); self-consistency checks live in tests/test_metrics_oracle.py.
+reference (no vectors); self-consistency checks live in tests/test_oracle.py (filter specification, scipy cross-checks)
+and tests/test_metrics_cpu.py (pystoi's dither against the zero rule, the Levinson recursion against the dense solve).
 """
 import numpy as np
 from scipy.signal import resample_poly
@@ -92,17 +93,64 @@ def stft_tob(x, obm):
     return np.sqrt(np.matmul(obm, np.square(np.abs(spec))))
 
 
-def row_col_normalize(x):
-    """x [J, 15, 30]; the EPS * randn dither of pystoi (2.2e-16) is omitted."""
+# A column of a segment is degenerate where its 15 normalised rows agree: in exact arithmetic its centred sum of squares is 0, in
+# float64 it is what rounding leaves, <= 1.2e-30 on every fixture of tests/test_metrics_cpu.py (entries of unit-norm rows are <= 1, their
+# rounding ~1e-16, 15 of them squared).  That happens beside every silent stretch of the estimate: a segment with ONE audible frame and
+# 29 silent ones has the same row [-a ... -a, 29 a] in every band.  Every other column of the same fixtures has a sum of squares of
+# 2.5e-5 or more (1.4e-3 on the regular ones), so any threshold between the two does; it is absolute because the rows are normalised.  (The rows themselves are not: there the rule
+# is the exact zero, which is what a silent band gives.)
+COL_SS_MIN = 1e-24
+
+
+def _unit_norm(xn, axis, ss_min):
+    ss = np.sum(np.square(xn), axis=axis, keepdims=True)
+    if ss_min is None:                           # the bare formula
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return xn / np.sqrt(ss)
+    ok = ss > ss_min
+    if np.all(ok):
+        return xn / np.sqrt(ss)
+    return np.where(ok, xn / np.sqrt(np.where(ok, ss, 1.0)), 0.0)
+
+
+def row_col_normalize(x, degenerate="zero", dither_rng=None):
+    """pystoi.utils.row_col_normalize on x [J, 15, 30]: each row (last axis) to zero mean and unit norm, then each column (axis 1).
+
+    pystoi adds ``EPS * randn`` (EPS = 2.2e-16) to x before the row step and again before the column step; that is why the
+    reference script seeds numpy.  ``dither_rng`` (anything with ``standard_normal(shape)``: a ``numpy.random.Generator`` or
+    ``RandomState``) restates those two additions, and then the formula is pystoi's, with no rule on top.  Without it there is no
+    dither, and a row or column whose centred sum of squares is 0 - an estimate that is exactly silent in a band for 30 frames,
+    or for 29 of them (COL_SS_MIN) - would be 0 / 0 or normalised rounding noise.  ``degenerate="zero"`` (the rule the kernels
+    follow) makes such a row or column all zeros; ``degenerate="nan"`` is the bare formula.  Where nothing is degenerate the two
+    are the same arithmetic, bit for bit.  What the dither is worth against the rule, on both kinds of input, is measured in
+    tests/test_metrics_cpu.py."""
+    assert degenerate in ("zero", "nan")
+    rule = degenerate == "zero" and dither_rng is None
+    if dither_rng is not None:
+        x = x + EPS * dither_rng.standard_normal(x.shape)
     xn = x - np.mean(x, axis=-1, keepdims=True)
-    xn = xn / np.sqrt(np.sum(np.square(xn), axis=-1, keepdims=True))
+    xn = _unit_norm(xn, -1, 0.0 if rule else None)
+    if dither_rng is not None:
+        xn = xn + EPS * dither_rng.standard_normal(xn.shape)
     xn = xn - np.mean(xn, axis=1, keepdims=True)
-    xn = xn / np.sqrt(np.sum(np.square(xn), axis=1, keepdims=True))
+    xn = _unit_norm(xn, 1, COL_SS_MIN if rule else None)
     return xn
 
 
-def estoi(x, y, fs_sig):
-    """pystoi.stoi(x, y, fs_sig, extended=True); x = clean, y = processed."""
+def estoi(x, y, fs_sig, degenerate="zero", dither_rng=None):
+    """pystoi.stoi(x, y, fs_sig, extended=True); x = clean, y = processed.  degenerate / dither_rng: see row_col_normalize
+    (x is normalised before y, so with a dither the draws go to x's rows, x's columns, y's rows, y's columns, as in pystoi)."""
+    seg = estoi_segments(x, y, fs_sig)
+    if seg is None:
+        return 1e-5            # pystoi warns "Not enough STFT frames" and returns 1e-5
+    xs, ys = seg
+    xn, yn = row_col_normalize(xs, degenerate, dither_rng), row_col_normalize(ys, degenerate, dither_rng)
+    return float(np.sum(xn * yn / N) / xn.shape[0])
+
+
+def estoi_segments(x, y, fs_sig):
+    """Everything of ``estoi`` in front of the normalisation: the third-octave segments (xs, ys), each [J, 15, 30], or None
+    where fewer than 30 frames are left."""
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     assert x.shape == y.shape
@@ -114,11 +162,10 @@ def estoi(x, y, fs_sig):
     x_tob, y_tob = stft_tob(x, obm), stft_tob(y, obm)
     M = x_tob.shape[1]
     if M < N:
-        return 1e-5            # pystoi warns "Not enough STFT frames" and returns 1e-5
+        return None
     xs = np.array([x_tob[:, m - N:m] for m in range(N, M + 1)])
     ys = np.array([y_tob[:, m - N:m] for m in range(N, M + 1)])
-    xn, yn = row_col_normalize(xs), row_col_normalize(ys)
-    return float(np.sum(xn * yn / N) / xn.shape[0])
+    return xs, ys
 
 
 def sdr(ref, est, filter_length=512, clamp_db=50.0):

@@ -103,43 +103,50 @@ __global__ void __launch_bounds__(256) tob_kernel(const float* __restrict__ xs, 
                                                   const int* __restrict__ lens, float* __restrict__ tobx,
                                                   float* __restrict__ toby, int L, int Mmax, FftPlan plan,
                                                   const float2* __restrict__ tw_g, TobBands bands) {
-  constexpr int NF = 4, n = 512;
-  __shared__ __attribute__((aligned(16))) float2 tw[n];
-  __shared__ __attribute__((aligned(16))) float2 bufA[NF * n];
-  __shared__ __attribute__((aligned(16))) float2 bufB[NF * n];
+  // Each real frame (256 samples, zero-padded to 512) goes through a 256-point complex FFT of ITS OWN even / odd samples
+  // (z[m] = f[2m] + i f[2m+1]; X[k] = E[k] + W_512^k O[k]), never packed with a frame of the other signal: a two-for-one FFT
+  // of (x, y) leaves |X| * 1e-7 of rounding residue in Y, which is all there is of Y where the estimate is silent - and the
+  // normalisation of estoi_kernel then correlates the reference with its own residue.  A zero frame comes out exactly zero.
+  constexpr int NF = 4, n = 256, NS = 2 * NF;
+  __shared__ __attribute__((aligned(16))) float2 tw[n];        // W_256^j
+  __shared__ __attribute__((aligned(16))) float2 tw2[n];       // W_512^k, k < 256
+  __shared__ __attribute__((aligned(16))) float2 bufA[NS * n];
+  __shared__ __attribute__((aligned(16))) float2 bufB[NS * n];
   const int p = blockIdx.y, m0 = blockIdx.x * NF, tid = threadIdx.x;
   const int Ls = lens[p];
   const int M = Ls > 256 ? (Ls - 256 + 127) / 128 : 0;
   if (m0 >= M) return;
-  for (int i = tid; i < n; i += 256) tw[i] = tw_g[i];
+  for (int i = tid; i < n; i += 256) { tw[i] = tw_g[2 * i]; tw2[i] = tw_g[i]; }
   const float* xp = xs + (long)p * L;
   const float* yp = ys + (long)p * L;
-  for (int idx = tid; idx < NF * n; idx += 256) {
-    const int f = idx >> 9, i = idx & 511;
-    float2 v = make_float2(0.f, 0.f);
-    if (i < 256 && m0 + f < M) {
-      const float wv = hann258(i);
-      const int o = (m0 + f) * 128 + i;
-      v = make_float2(wv * xp[o], wv * yp[o]);
+  for (int idx = tid; idx < NF * n; idx += 256) {   // sequence 2 * frame + signal; the two signals share the window values
+    const int f = idx >> 8, i = idx & 255;
+    float2 vx = make_float2(0.f, 0.f), vy = vx;
+    if (i < 128 && m0 + f < M) {
+      const float w0 = hann258(2 * i), w1 = hann258(2 * i + 1);
+      const int o = (m0 + f) * 128 + 2 * i;         // o + 1 <= (M - 1) * 128 + 255 < Ls
+      vx = make_float2(w0 * xp[o], w1 * xp[o + 1]);
+      vy = make_float2(w0 * yp[o], w1 * yp[o + 1]);
     }
-    bufA[idx] = v;
+    bufA[(2 * f) * n + i] = vx;
+    bufA[(2 * f + 1) * n + i] = vy;
   }
   __syncthreads();
-  const float2* Z = fft_lds_forward(bufA, bufB, NF, plan, tw);
-  // 15 bands x NF frames x 2 signals: one thread per (frame, band)
-  for (int idx = tid; idx < NF * 15; idx += 256) {
-    const int f = idx / 15, b = idx - f * 15;
+  const float2* Z = fft_lds_forward(bufA, bufB, NS, plan, tw);
+  // 15 bands x NF frames x 2 signals: one thread per (frame, band, signal); k < bands.hi <= 256 (the host picks edges among bins 0..256)
+  for (int idx = tid; idx < NF * 30; idx += 256) {
+    const int f = idx / 30, r = idx - f * 30, g = r / 15, b = r - g * 15;
     if (m0 + f >= M) continue;
-    float sx = 0.f, sy = 0.f;
+    const float2* Zs = Z + (2 * f + g) * n;
+    float acc = 0.f;
     for (int k = bands.lo[b]; k < bands.hi[b]; ++k) {
-      const float2 zk = Z[f * n + k], zc = Z[f * n + (k == 0 ? 0 : n - k)];
-      const float xr = 0.5f * (zk.x + zc.x), xi = 0.5f * (zk.y - zc.y);
-      const float yr = 0.5f * (zk.y + zc.y), yi = -0.5f * (zk.x - zc.x);
-      sx += xr * xr + xi * xi;
-      sy += yr * yr + yi * yi;
+      const float2 zk = Zs[k], zc = Zs[(n - k) & (n - 1)], w = tw2[k];
+      const float er = 0.5f * (zk.x + zc.x), ei = 0.5f * (zk.y - zc.y);
+      const float orr = 0.5f * (zk.y + zc.y), oi = -0.5f * (zk.x - zc.x);
+      const float re = er + (w.x * orr - w.y * oi), im = ei + (w.x * oi + w.y * orr);
+      acc += re * re + im * im;
     }
-    tobx[((long)p * 15 + b) * Mmax + m0 + f] = sqrtf(sx);
-    toby[((long)p * 15 + b) * Mmax + m0 + f] = sqrtf(sy);
+    (g ? toby : tobx)[((long)p * 15 + b) * Mmax + m0 + f] = sqrtf(acc);
   }
 }
 
@@ -174,7 +181,7 @@ __global__ void __launch_bounds__(256) estoi_kernel(const float* __restrict__ to
       mu /= 30.0;
       double ss = 0.0;
       for (int c = 0; c < 30; ++c) { const double v = sg[b][c] - mu; ss += v * v; }
-      const double inv = 1.0 / sqrt(ss);
+      const double inv = ss > 0.0 ? 1.0 / sqrt(ss) : 0.0;   // a constant row (estimate silent in this band) -> zeros, not 0 * inf
       for (int c = 0; c < 30; ++c) sg[b][c] = (sg[b][c] - mu) * inv;
     }
     __builtin_amdgcn_wave_barrier();
@@ -189,7 +196,9 @@ __global__ void __launch_bounds__(256) estoi_kernel(const float* __restrict__ to
         const double vx = segx[w][b][c] - mx, vy = segy[w][b][c] - my;
         sx += vx * vx; sy += vy * vy; sxy += vx * vy;
       }
-      part = sxy / (sqrt(sx) * sqrt(sy));
+      // a column whose 15 normalised rows agree (one audible frame beside 29 silent ones: the same row in every band) is 0 in
+      // exact arithmetic and <= 1e-30 of rounding here, against >= 1e-5 anywhere else: zeros too (metrics_ref.COL_SS_MIN)
+      part = (sx > 1e-24 && sy > 1e-24) ? sxy / (sqrt(sx) * sqrt(sy)) : 0.0;
     }
     total += part;
     __builtin_amdgcn_wave_barrier();
@@ -334,7 +343,7 @@ extern "C" int urse_estoi_batch(const float* ref10k, const float* inf10k, float*
     tb.hi[k] = bh;
   }
   FftPlan plan;
-  make_fft_plan(512, &plan);
+  make_fft_plan(256, &plan);   // (a 512-point real transform as a 256-point complex one: tob_kernel)
   const int Mmax = nfr > 0 ? nfr : 1;
   hipLaunchKernelGGL(tob_kernel, dim3(ceil_div(Mmax, 4), P), dim3(256), 0, st, ws_x, ws_y, lens, tob_x, tob_y, L, Mmax,
                      plan, reinterpret_cast<const float2*>(tw512), tb);
